@@ -8,10 +8,19 @@ engine over the N GPUs (layer split by tensor_split 1:...:1, stage streams handi
 by RCCL send/recv, the greedy token moved home to stage 0 by a device copy); the other ranks only
 bracket the run with barriers.  value = tokens/s of the whole pipeline.
 
-Adds:
-  roofline     -- dominant decode kernel (Q4_K gate|up mat-vec, 4096 x 2*14336), HIP-event timed
-  cpu_baseline -- the REFERENCE ggml CPU path (oracle/_ref/ref_llama, built from the reference
-                  sources) on the same synthetic 8B weights, bounded sample, rank 0 only.
+A plain run sets up, warms up, times --steps decode tokens and prints the result line.  When the context fills
+before the timed steps are done, decoding goes on from the first timed position again (the same positions, the
+cache rows overwritten), so every timed step is a decode token at that context depth and --steps is the number timed.
+
+--dump-outputs DIR writes what the last timed step handed back, after the timing: DIR/logits.npy (float32, the last
+step's logits) and DIR/tokens.npy (float64, every timed step's greedy token, the last step's last).  Weights, prompt
+and seeds are fixed, so the inputs are the same from run to run.
+
+--full adds (each a run of its own, after the timed steps):
+  roofline      -- dominant decode kernel (Q4_K gate|up mat-vec, 4096 x 2*14336), HIP-event timed
+  generate_path -- the same workload through load_model() + generate() of the drop-in C ABI
+  cpu_baseline  -- the REFERENCE ggml CPU path (oracle/_ref/ref_llama, built from the reference
+                   sources) on the same synthetic 8B weights, bounded sample, rank 0 only.
 """
 import argparse
 import json
@@ -210,9 +219,21 @@ def generate_path(hp, types, n_prompt, n_gen, ubatch, seed=1234):
                    "get_last_eval_time and 1000 / get_last_process_time (ms per token)"}
 
 
-def run_model(K, torch, hp, types, n_prompt, ubatch, steps, warmup):
+def dump_outputs(K, m, toks, out_dir):
+    """--dump-outputs: what the last timed step handed back (its logits, read from the device after the timing) and
+    every timed step's greedy token"""
+    import ctypes
+    logits = np.empty(m.hp["n_vocab"], np.float32)
+    K.call("kcpp_model_read_logits", m.m, logits.ctypes.data_as(ctypes.c_void_p))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "logits.npy"), logits)
+    np.save(os.path.join(out_dir, "tokens.npy"), np.asarray(toks, dtype=np.float64))
+
+
+def run_model(K, torch, hp, types, n_prompt, ubatch, steps, warmup, dump=None):
     """koboldcpp --benchmark semantics on one GPU: prefill n_prompt ids (" 1" pattern) in ubatches, then
-    greedy decode (graph replay + on-device argmax per token).  Weights and inputs resident before timing."""
+    greedy decode (graph replay + on-device argmax per token).  Weights and inputs resident before timing.
+    When the context is full the decode goes on from the first timed position (see the module docstring)."""
     m = K.Model(hp, types, max_ubatch=ubatch)
     m.synth(1234)
     prompt = [16 + (i % 2) for i in range(n_prompt)]
@@ -228,23 +249,32 @@ def run_model(K, torch, hp, types, n_prompt, ubatch, steps, warmup):
     for _ in range(warmup):
         m.decode_greedy(n_past)
         n_past += 1
-    steps = min(steps, hp["n_ctx"] - n_past)
+    p0 = n_past                           # first timed position
+    if steps < 1 or p0 >= hp["n_ctx"]:
+        raise SystemExit("bench.py: no timed step fits (--steps %d, prompt + warm-up %d of n_ctx %d)" % (steps, p0, hp["n_ctx"]))
     torch.cuda.synchronize()
     # every token comes back to the host, one step behind the device (the next step is queued while the host reads
     # the previous token: kcpp_model_decode_greedy_lagged); the timed region ends when the last token is on the host
     toks = []
     t0 = time.perf_counter()
+    pos_sum = 0
     for _ in range(steps):
+        if n_past == hp["n_ctx"]:
+            n_past = p0                   # context full: decode on from the first timed position
         toks.append(m.decode_greedy_lagged(n_past))
+        pos_sum += n_past
         n_past += 1
     toks.append(m.greedy_drain())
     torch.cuda.synchronize()
     t_tg = time.perf_counter() - t0
     assert toks[0] == -1 and min(toks[1:]) >= 0 and len(toks) == steps + 1
     wb = m.weight_bytes()
+    if dump:
+        dump_outputs(K, m, toks[1:], dump)
     m.close()
+    # kv_len: cached positions attended per timed step, at the middle of the step (p0 + steps / 2 without a wrap)
     return {"dec": steps / t_tg, "pre": n_prompt / t_pp, "t_pp": t_pp, "ms_step": t_tg / steps * 1e3, "steps": steps,
-            "n_past": n_past, "wb": wb}
+            "n_past": min(p0 + steps, hp["n_ctx"]), "kv_len": pos_sum / steps + 0.5, "wb": wb}
 
 
 def other_config(args, K, torch):
@@ -256,7 +286,7 @@ def other_config(args, K, torch):
         hp = dict(LLAMA3_8B)
         types = R.uniform_types(hp["n_layer"], R.Q8_0)
         n_prompt, ub = (args.prompt if args.prompt != 3840 else 1024), 32
-        r = run_model(K, torch, hp, types, n_prompt, ub, min(args.steps, 64), args.warmup)
+        r = run_model(K, torch, hp, types, n_prompt, ub, min(args.steps, 64), args.warmup, args.dump_outputs)
         # bytes per ubatch: every layer weight once (the Q8_0 output head runs once per llama_decode call)
         shapes = R.weight_shapes(hp)
         layer_bytes = sum(R.row_bytes(t, k) * n for i, ((k, n), t) in enumerate(zip(shapes, types)) if i >= 3)
@@ -277,7 +307,7 @@ def other_config(args, K, torch):
         hp = dict(MIXTRAL_8X7B)
         types = R.mixtral_q5_k_m_types(hp["n_layer"])
         n_prompt = args.prompt if args.prompt != 3840 else 512
-        r = run_model(K, torch, hp, types, n_prompt, args.ubatch, args.steps, args.warmup)
+        r = run_model(K, torch, hp, types, n_prompt, args.ubatch, args.steps, args.warmup, args.dump_outputs)
         shapes = R.weight_shapes(hp)
         tok_bytes = 0
         for i, ((k, n), t) in enumerate(zip(shapes, types)):
@@ -285,7 +315,7 @@ def other_config(args, K, torch):
                 continue                   # token embedding: one row gathered
             b = R.row_bytes(t, k) * n
             tok_bytes += b * (hp["n_expert_used"] if R.n_slices(hp, i) > 1 else 1)
-        kv = 2 * hp["n_layer"] * hp["n_head_kv"] * (hp["n_embd"] // hp["n_head"]) * 2 * (r["n_past"] - r["steps"] / 2)
+        kv = 2 * hp["n_layer"] * hp["n_head_kv"] * (hp["n_embd"] // hp["n_head"]) * 2 * r["kv_len"]
         gbs = (tok_bytes + kv) / (r["ms_step"] * 1e-3) / 1e9
         return {"metric": "decode tok/s (Mixtral-8x7B Q5_K_M, top-2 of 8 experts)", "value": round(r["dec"], 2),
                 "unit": "tok/s", "n_gpus": 1, "steps": r["steps"], "warmup": args.warmup,
@@ -296,6 +326,8 @@ def other_config(args, K, torch):
                 "prefill_tok_s": round(r["pre"], 1), "weight_bytes": r["wb"], "bytes_per_token": tok_bytes,
                 "decode_effective_GBps": round(gbs, 1), "decode_hbm_frac": round(gbs / HBM_PEAK_GBS, 4)}
     if args.config == "llama3-70b-stage":
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs needs a whole model (this stage has no output head)")
         return stage70b(args, K, torch)
     raise SystemExit("unknown --config %s" % args.config)
 
@@ -380,9 +412,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--prompt", type=int, default=3840)
     ap.add_argument("--ubatch", type=int, default=512)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline kernel, the generate() leg and the reference "
+                         "CPU baseline (the roofline, generate_path and cpu_baseline objects of the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's logits (logits.npy, float32) and every timed step's greedy token "
+                         "(tokens.npy, float64) into DIR after the timing")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the reference CPU baseline")
     ap.add_argument("--no-generate-path", action="store_true",
-                    help="skip the generate() leg (koboldcpp --benchmark through the C ABI)")
+                    help="with --full: skip the generate() leg (koboldcpp --benchmark through the C ABI)")
     ap.add_argument("--cpu-threads", type=int, default=16)
     ap.add_argument("--roofline-only", action="store_true",
                     help="only the dominant-kernel timing (for the rocprofv3 --pmc passes in profiles/)")
@@ -428,17 +466,32 @@ def run_bench(args, K, torch, n_dev):
         hp["n_layer"] = args.layers
     types = q4_k_m_types(hp["n_layer"])
     if n_dev == 1:
-        r = run_model(K, torch, hp, types, args.prompt, args.ubatch, args.steps, args.warmup)
+        r = run_model(K, torch, hp, types, args.prompt, args.ubatch, args.steps, args.warmup, args.dump_outputs)
         par = "single GPU"
     else:
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs needs --gpus 1 (the multi-GPU engine keeps its tokens on the devices)")
         # the drop-in engine load_model ships (koboldcpp_amd/csrc/expose.cpp): n_dev layer-split stages in this one
         # process, RCCL send/recv hand-off between the stage streams, pipelined prefill ubatches, greedy steps with
         # the argmax on the last stage and the token moved home to stage 0 by a 4-byte device copy (expose.cpp
         # greedy_step / token_home: no host synchronisation inside a step)
-        steps = min(args.steps, hp["n_ctx"] - args.prompt - args.warmup - 1)
-        e = K.engine_bench(hp, types, n_dev, args.prompt, args.ubatch, args.warmup, steps)
-        r = {"dec": steps / e["decode_s"], "pre": args.prompt / e["prefill_s"], "t_pp": e["prefill_s"],
-             "ms_step": e["decode_s"] / steps * 1e3, "steps": steps, "n_past": e["n_past"], "wb": weight_bytes(hp, types)}
+        # the engine decodes on to the end of the context at most: more steps than that are timed as further runs
+        # of the engine over the same positions, their decode times added up (the prefill time is the first run's)
+        room = hp["n_ctx"] - args.prompt - args.warmup - 1
+        steps = args.steps
+        if steps < 1 or room < 1:
+            raise SystemExit("bench.py: no timed step fits (--steps %d, %d positions left of n_ctx %d)" % (steps, room, hp["n_ctx"]))
+        e, dec_s, kv_sum, left = None, 0.0, 0.0, steps
+        while left > 0:
+            n = min(left, room)
+            e1 = K.engine_bench(hp, types, n_dev, args.prompt, args.ubatch, args.warmup, n)
+            e = e or e1
+            dec_s += e1["decode_s"]
+            kv_sum += n * (e1["n_past"] - n / 2)
+            left -= n
+        r = {"dec": steps / dec_s, "pre": args.prompt / e["prefill_s"], "t_pp": e["prefill_s"],
+             "ms_step": dec_s / steps * 1e3, "steps": steps, "n_past": e["n_past"], "kv_len": kv_sum / steps,
+             "wb": weight_bytes(hp, types)}
         par = "layer split over %d GPUs (tensor_split 1:...:1), %s hand-off, one process" % (
             n_dev, "RCCL send/recv" if e["rccl"] else "event-ordered peer copy")
     print(json.dumps(bench_line(args, K, torch, hp, types, r, n_dev, par)))
@@ -450,7 +503,7 @@ def bench_line(args, K, torch, hp, types, r, n_dev, par):
     # position; token_embd is a 1-row gather, not streamed, so it is excluded)
     import refharness as R
     embd_bytes = R.row_bytes(types[0], hp["n_embd"]) * hp["n_vocab"]
-    kv_bytes = 2 * hp["n_layer"] * hp["n_head_kv"] * (hp["n_embd"] // hp["n_head"]) * 2 * (n_past - steps / 2)
+    kv_bytes = 2 * hp["n_layer"] * hp["n_head_kv"] * (hp["n_embd"] // hp["n_head"]) * 2 * r["kv_len"]
     token_gbs = (wb - embd_bytes + kv_bytes) / (ms_step * 1e-3) / 1e9
     # prefill roofline: F(n) = 2 * (layer weight elements) * n + attention 2 * 2 * n_head * D
     # * n(n+1)/2 per layer (causal QK^T and PV) + the output head once (only the last logits are computed)
@@ -460,7 +513,6 @@ def bench_line(args, K, torch, hp, types, r, n_dev, par):
     attn_flops = 4 * hp["n_layer"] * hp["n_embd"] * n * (n + 1) / 2
     pre_flops = 2 * layer_elems * n + attn_flops + 2 * hp["n_embd"] * hp["n_vocab"]
     pre_tflops = pre_flops / t_pp / 1e12
-    roof = measure_roofline(K, torch)
     out = {
         "metric": "decode tok/s (Llama-3-8B Q4_K_M, 4k ctx); prefill tok/s in prefill_tok_s",
         "value": round(dec, 2), "unit": "tok/s", "n_gpus": n_dev, "steps": steps, "warmup": args.warmup,
@@ -474,7 +526,6 @@ def bench_line(args, K, torch, hp, types, r, n_dev, par):
         "decode_effective_GBps": round(token_gbs, 1), "decode_hbm_frac": round(token_gbs / HBM_PEAK_GBS, 4),   # one stage streams at a time
         "decode_bytes_per_token": int(wb - embd_bytes + kv_bytes),
         "weight_bytes_resident": wb,
-        "roofline": roof,
         "prefill_roofline": {"bound": "mfma", "achieved": round(pre_tflops, 1), "peak": MFMA_F16_PEAK_TFLOPS * n_dev,
                              "unit": "TFLOP/s", "frac": round(pre_tflops / MFMA_F16_PEAK_TFLOPS / n_dev, 4),
                              # the Q4_K / Q5_K GEMMs run v_mfma_i32_32x32x32_i8 (2x the f16 rate per clock,
@@ -485,6 +536,9 @@ def bench_line(args, K, torch, hp, types, r, n_dev, par):
                                                                "peak = %d GPU(s); frac vs the dense f16 peak, frac_i8 "
                                                                "vs the dense i8 peak" % n_dev},
     }
+    if not args.full:
+        return out
+    out["roofline"] = measure_roofline(K, torch)
     if n_dev == 1 and not args.no_generate_path:
         try:
             out["generate_path"] = generate_path(hp, types, args.prompt, 256, args.ubatch)

@@ -4,7 +4,7 @@
 # usage: tools/pmc_prefill.sh OUTDIR        summary: python tools/pmc_prefill_summary.py OUTDIR
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=$1; mkdir -p $out
-B="bench.py --no-cpu-baseline --steps 2 --warmup 1"
+B="bench.py --full --no-cpu-baseline --steps 2 --warmup 1"
 timeout -k 10 120 rocprofv3 --list-avail > $out/avail.txt 2>&1 || true
 i=0
 for grp in "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY GRBM_GUI_ACTIVE" \

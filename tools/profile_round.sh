@@ -19,7 +19,7 @@ FA_VARIANTS=3 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -
 FA_VARIANTS=3 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/fa_write -o fa -- python3 tools/fa_dec_bench.py 3850 > $OUT/fa_write.log 2>&1 &&
 FA_VARIANTS=3 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/fa_trace -o fa -- python3 tools/fa_dec_bench.py 3850 > $OUT/fa_trace.log 2>&1 &&
 # 4: kernel-trace stats of a short full bench (prefill + decode), no CPU baseline
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o bench -- python3 bench.py --steps 32 --warmup 4 --no-cpu-baseline > $OUT/bench.log 2>&1
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o bench -- python3 bench.py --full --steps 32 --warmup 4 --no-cpu-baseline > $OUT/bench.log 2>&1
 rc=$?
 echo "profile_round rc=$rc"
 exit $rc
