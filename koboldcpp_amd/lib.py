@@ -135,6 +135,7 @@ _SIGS = {
     "kcpp_gemm_grouped": [I, P, P, I64, I64, I64, P, I64, P, P, I, P, P, I, P, P],
     "kcpp_gemm_grouped_ws_bytes": [I, I64, I64, I],
     "kcpp_flash_attn_exact": [P, P, P, P, I, I, I, I, I, P, Fl, P],
+    "kcpp_flash_attn_ext_exact": [P, I64, I64, P, P, P, I64, P, I, I, I, I, I, Fl, P],
     "kcpp_model_weight_bytes": [P],
     "kcpp_model_set_kv_types": [P, I, I],
     "kcpp_rope_qk_inplace": [P, I64, I, I, I, I, I, P, P, P],

@@ -1062,7 +1062,11 @@ void orc_rope(const float *x, float *y, int64_t head_dim, int64_t n_heads, int64
 static int g_fa_f32_accum = 0;
 void orc_set_fa_f32_accum(int on) { g_fa_f32_accum = on; }
 
-/* ggml_compute_forward_flash_attn_ext_f16, F16 K/V branch (ggml.c:15667-15875) */
+/* ggml_compute_forward_flash_attn_ext_f16, F16 K/V branch (ggml.c:15667-15875), NOT in the reference's strict
+ * order: the q.k dot is summed in double (dot_f16), where the reference's AVX2 build sums it in f32 in its vector
+ * order.  The f16 accumulator amplifies that difference, so this function agrees with the reference build only to
+ * ~2e-3 (tests/test_oracle_golden.py::test_flash_attn); orc_flash_attn_ext_strict below is the bit-exact one.  The
+ * e2e oracle baselines are made with this one and must not move. */
 void orc_flash_attn_ext(const float *q, const uint16_t *k, const uint16_t *v, int64_t kv_stride,
                         const uint16_t *mask, float *out, int D, int n_q, int n_head,
                         int n_kv, int n_head_kv, float scale, int nthreads) {
@@ -1104,6 +1108,71 @@ void orc_flash_attn_ext(const float *q, const uint16_t *k, const uint16_t *v, in
         const float S_inv = 1.0f / S;
         float *po = out + ((int64_t)iq1 * n_head + h) * D;
         for (int d = 0; d < D; ++d) po[d] = vkq32[d] * S_inv;
+    }
+}
+
+/* ggml_vec_dot_f16 as the reference's AVX2 / F16C / FMA build computes it (ggml.c:2258-2290 with the GGML_F16_*
+ * macros of :1443-1462 and GGML_F32x8_REDUCE, :1413-1431): GGML_F16_STEP = 32 elements per iteration into
+ * 4 accumulators of 8 f32 lanes by fused multiply-add, then x0 += x2, x1 += x3, x0 += x1, the two 128-bit halves
+ * added, and two horizontal adds: (t0 + t1) + (t2 + t3).  Elements past the last whole step are added in double. */
+static float dot_f16_strict(int n, const uint16_t *x, const uint16_t *y) {
+    float acc[4][8];
+    for (int a = 0; a < 4; ++a) for (int l = 0; l < 8; ++l) acc[a][l] = 0.0f;
+    const int np = n & ~31;
+    for (int i = 0; i < np; i += 32)
+        for (int a = 0; a < 4; ++a)
+            for (int l = 0; l < 8; ++l)
+                acc[a][l] = fmaf(H2F(x[i + a * 8 + l]), H2F(y[i + a * 8 + l]), acc[a][l]);
+    for (int l = 0; l < 8; ++l) { acc[0][l] = acc[0][l] + acc[2][l]; acc[1][l] = acc[1][l] + acc[3][l]; }
+    for (int l = 0; l < 8; ++l) acc[0][l] = acc[0][l] + acc[1][l];
+    const float t0 = acc[0][0] + acc[0][4], t1 = acc[0][1] + acc[0][5], t2 = acc[0][2] + acc[0][6],
+                t3 = acc[0][3] + acc[0][7];
+    double sumf = (double)((t0 + t1) + (t2 + t3));
+    for (int i = np; i < n; ++i) sumf += (double)(H2F(x[i]) * H2F(y[i]));
+    return (float)sumf;
+}
+
+/* orc_flash_attn_ext in the reference build's exact arithmetic order: the dot of dot_f16_strict, glibc expf, the
+ * f16 scale / mad of the VKQ16 accumulator, -inf keys skipped, any other mask value added after the scaling
+ * (s = s*scale; s += mv).  Bit-equal to the reference build's ggml_flash_attn_ext (tests/test_fa_strict_oracle.py),
+ * so it can stand in for it as the expected value of the strict-parity kernel (csrc/attn_exact.hip).
+ * q: row (t, h) at (const char *)q + t*q_nb1 + h*q_nb2 (bytes); mask row t at mask + t*mask_ld (elements). */
+void orc_flash_attn_ext_strict(const float *q, int64_t q_nb1, int64_t q_nb2, const uint16_t *k, const uint16_t *v,
+                               int64_t kv_stride, const uint16_t *mask, int64_t mask_ld, float *out, int D, int n_q,
+                               int n_head, int n_kv, int n_head_kv, float scale, int nthreads) {
+    const int rk = n_head / n_head_kv;
+    if (nthreads <= 0) nthreads = omp_get_max_threads();
+    #pragma omp parallel for num_threads(nthreads) schedule(dynamic, 1)
+    for (int ir = 0; ir < n_q * n_head; ++ir) {
+        const int iq1 = ir / n_head, h = ir % n_head;
+        const int hk = h / rk;
+        uint16_t qh[512];
+        uint16_t vkq16[512];
+        const float *pq = (const float *)((const char *)q + iq1 * q_nb1 + h * q_nb2);
+        for (int d = 0; d < D; ++d) { qh[d] = F2H(pq[d]); vkq16[d] = 0; }
+        float S = 0.0f, M = -INFINITY;
+        for (int ic = 0; ic < n_kv; ++ic) {
+            const float mv = mask ? H2F(mask[iq1 * mask_ld + ic]) : 0.0f;
+            if (mv == -INFINITY) continue;
+            float s = dot_f16_strict(D, k + (int64_t)ic * kv_stride + (int64_t)hk * D, qh);
+            s = s * scale;
+            s += mv;
+            const float Mold = M;
+            float ms = 1.0f, vs = 1.0f;
+            const uint16_t *vr = v + (int64_t)ic * kv_stride + (int64_t)hk * D;
+            if (s > M) {
+                M = s;
+                ms = expf(Mold - M);
+                for (int d = 0; d < D; ++d) vkq16[d] = F2H(H2F(vkq16[d]) * ms);            /* ggml_vec_scale_f16 */
+            } else {
+                vs = expf(s - M);
+            }
+            for (int d = 0; d < D; ++d) vkq16[d] = F2H(fmaf(H2F(vr[d]), vs, H2F(vkq16[d])));   /* ggml_vec_mad_f16 */
+            S = S * ms + vs;
+        }
+        const float S_inv = 1.0f / S;
+        float *po = out + ((int64_t)iq1 * n_head + h) * D;
+        for (int d = 0; d < D; ++d) po[d] = H2F(vkq16[d]) * S_inv;
     }
 }
 

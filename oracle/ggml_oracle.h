@@ -51,12 +51,21 @@ void orc_rope(const float *x, float *y, int64_t head_dim, int64_t n_heads, int64
               const float *freq_factors, float ext_factor, float attn_factor,
               float beta_fast, float beta_slow, int n_ctx_orig);
 
-/* ggml_compute_forward_flash_attn_ext_f16 with F16 K/V (ggml.c:15667-15860).
+/* ggml_compute_forward_flash_attn_ext_f16 with F16 K/V (ggml.c:15667-15860), the NON-strict restatement: the q.k
+ * dot is summed in double, so it follows the reference build only to ~2e-3 (the f16 accumulator amplifies the
+ * difference); the e2e oracle baselines use it.
  * q   [n_q][n_head][D] f32, k/v [n_kv][n_head_kv][D] f16 (row stride kv_stride elements),
  * mask [n_q][n_kv] f16 (may be NULL), out [n_q][n_head][D] f32 */
 void orc_flash_attn_ext(const float *q, const uint16_t *k, const uint16_t *v, int64_t kv_stride,
                         const uint16_t *mask, float *out, int D, int n_q, int n_head,
                         int n_kv, int n_head_kv, float scale, int nthreads);
+
+/* the same in the reference AVX2 build's exact order (ggml_vec_dot_f16's 4 x 8 FMA accumulators and reduce tree):
+ * bit-equal to the reference build's ggml_flash_attn_ext.  q row (t, h) at byte offset t*q_nb1 + h*q_nb2; mask row
+ * stride mask_ld elements; mask values other than 0 / -inf are added after the scaling. */
+void orc_flash_attn_ext_strict(const float *q, int64_t q_nb1, int64_t q_nb2, const uint16_t *k, const uint16_t *v,
+                               int64_t kv_stride, const uint16_t *mask, int64_t mask_ld, float *out, int D, int n_q,
+                               int n_head, int n_kv, int n_head_kv, float scale, int nthreads);
 
 /* the same with a quantized K and V (Q8_0 / Q4_0 ggml block rows; ggml.c:15748-15851): Q quantized to Q8_0,
  * integer-block dot, V dequantized and accumulated in f32.  Row p of kv head hk at base + p*row_bytes +

@@ -50,6 +50,7 @@ def lib():
         L.orc_rms_norm.argtypes = [P, P, P, I64, I64, F]
         L.orc_rope.argtypes = [P, P, I64, I64, I64, P, I, F, F, P, F, F, F, F, I]
         L.orc_flash_attn_ext.argtypes = [P, P, P, I64, P, P, I, I, I, I, I, F, I]
+        L.orc_flash_attn_ext_strict.argtypes = [P, I64, I64, P, P, I64, P, I64, P, I, I, I, I, I, F, I]
         L.orc_synth_fill.argtypes = [I, ctypes.c_uint64, ctypes.c_uint64, I64, P]
         L.orc_llama_create.argtypes = [P, P, P, I]
         L.orc_llama_create.restype = P
@@ -116,7 +117,8 @@ def rope(x, pos, base, freq_scale=1.0):
 
 
 def flash_attn(q, k, v, mask, nthreads=0):
-    """q [T][H][D] f32; k,v [n_kv][HKV][D] f16 (uint16 view ok); mask [T][n_kv] f16 or None."""
+    """q [T][H][D] f32; k,v [n_kv][HKV][D] f16 (uint16 view ok); mask [T][n_kv] f16 or None.
+    The NON-strict restatement (q.k summed in double): within 2e-3 of the reference; flash_attn_strict is bit-equal."""
     q = np.ascontiguousarray(q, dtype=np.float32)
     T, H, D = q.shape
     k = np.ascontiguousarray(k).view(np.uint16)
@@ -127,6 +129,111 @@ def flash_attn(q, k, v, mask, nthreads=0):
     lib().orc_flash_attn_ext(ptr(q), ptr(k), ptr(v), HKV * D, m, ptr(out), D, T, H, n_kv, HKV,
                              1.0 / np.sqrt(D), nthreads)
     return out
+
+
+def flash_attn_strict(q, k, v, mask, q_strides=None, mask_ld=None, nthreads=0):
+    """orc_flash_attn_ext_strict: the reference AVX2 build's attention bit for bit (tests/test_fa_strict_oracle.py).
+    q f32 [T][H][D], or any f32 array with q_strides = (bytes per t, bytes per h) and shape given by out;
+    k, v [n_kv][HKV][D] f16 (uint16 view ok); mask f16 [rows >= T][mask_ld or n_kv] or None (values other than
+    0 / -inf are added to the scaled score).  Returns [T][H][D] f32."""
+    q = np.asarray(q, dtype=np.float32)
+    T, H, D = q.shape
+    if q_strides is None:
+        q = np.ascontiguousarray(q)
+        q_strides = (H * D * 4, D * 4)
+    else:
+        assert all(n == 1 or s == w for n, s, w in zip(q.shape, q.strides, (q_strides[0], q_strides[1], 4)))
+    k = np.ascontiguousarray(k).view(np.uint16)
+    v = np.ascontiguousarray(v).view(np.uint16)
+    n_kv, HKV, _ = k.shape
+    out = np.empty((T, H, D), np.float32)
+    m = None
+    if mask is not None:
+        mask = np.ascontiguousarray(mask).view(np.uint16)
+        mask_ld = mask.shape[1] if mask_ld is None else mask_ld
+        assert mask.shape[0] >= T and mask.shape[1] == mask_ld >= n_kv
+        m = ptr(mask)
+    lib().orc_flash_attn_ext_strict(ptr(q), q_strides[0], q_strides[1], ptr(k), ptr(v), HKV * D, m, mask_ld or 0,
+                                    ptr(out), D, T, H, n_kv, HKV, np.float32(1) / np.sqrt(np.float32(D)), nthreads)
+    return out
+
+
+# ---- strict-order attention cases (tests/golden/fa_long.npz, tests/test_fa_strict_oracle.py, tests/test_gpu_fa_exact.py)
+# Every input comes from integer hashes (below), so a case is its parameters.  Row t of the mask leaves keys
+# [0, n_past + t] live; then "dead" (lo, hi) key ranges are -inf for every row, "finite" puts f16 values in (-2, 0] on
+# the live keys, "holes" makes the mask non-causal: every key of [0, n_kv) live except a hashed 20 %.
+# n_past + T < n_kv: the view is padded with cells that no row sees (the 768-cell view over 701 keys).
+# "fixture": the expected output is the reference build's own, in fa_long.npz; otherwise flash_attn_strict's.
+FA_CASES = {
+    "kv512":        dict(T=1, H=8, HKV=2, D=128, n_kv=512, n_past=511),          # exactly one EX_CH chunk
+    "kv513":        dict(T=1, H=8, HKV=2, D=128, n_kv=513, n_past=512),          # one key into the second chunk
+    "kv1024_t4":    dict(T=4, H=8, HKV=2, D=128, n_kv=1024, n_past=1020),        # rows end at 1021..1024 keys
+    "kv1537_gqa1":  dict(T=2, H=4, HKV=4, D=128, n_kv=1537, n_past=1535),        # four chunks, GQA ratio 1
+    "live701_768":  dict(T=1, H=8, HKV=2, D=128, n_kv=768, n_past=700),          # the layer test's 700-key decode
+    "kv3840":       dict(T=1, H=2, HKV=1, D=128, n_kv=3840, n_past=3839),
+    "d64_kv513":    dict(T=3, H=8, HKV=1, D=64, n_kv=513, n_past=510),           # head dim 64, GQA ratio 8
+    "peaked":       dict(T=1, H=8, HKV=2, D=128, n_kv=777, n_past=776, q_amp=4),
+    "prefix_dead":  dict(T=2, H=8, HKV=2, D=128, n_kv=530, n_past=528, dead=[(0, 10)]),
+    "chunk2_dead":  dict(T=2, H=4, HKV=1, D=128, n_kv=1101, n_past=1099, dead=[(512, 1024)]),
+    "finite_mask":  dict(T=2, H=8, HKV=2, D=128, n_kv=640, n_past=638, finite=True),
+    "holes600":     dict(T=3, H=8, HKV=2, D=128, n_kv=600, holes=True, fixture=False),
+    "holes1100":    dict(T=2, H=4, HKV=1, D=128, n_kv=1100, holes=True, fixture=False),
+    "holes1100_d64": dict(T=2, H=8, HKV=2, D=64, n_kv=1100, holes=True, finite=True, fixture=False),
+}
+FA_FIXTURE_CASES = [n for n, c in FA_CASES.items() if c.get("fixture", True)]
+# the mask is exactly the runtime form's implicit causal window [0, n_past + t]
+FA_CAUSAL_CASES = [n for n, c in FA_CASES.items() if not (c.get("holes") or c.get("dead") or c.get("finite"))]
+
+
+def _hash64(seed, stream, n):
+    """n uint64 hashes (splitmix64 finalizer of a counter): integer arithmetic only, the same on every numpy"""
+    with np.errstate(over="ignore"):
+        x = np.arange(n, dtype=np.uint64) + np.uint64(seed) * np.uint64(0x9E3779B97F4A7C15) \
+            + np.uint64(stream) * np.uint64(0xD1B54A32D192ED03)
+        x ^= x >> np.uint64(30)
+        x *= np.uint64(0xBF58476D1CE4E5B9)
+        x ^= x >> np.uint64(27)
+        x *= np.uint64(0x94D049BB133111EB)
+        x ^= x >> np.uint64(31)
+    return x
+
+
+def _hash_bell(seed, stream, n):
+    """n integers in [-131070, 131070], the sum of the hash's four 16-bit fields centred: a bell shape, std 37837"""
+    h = _hash64(seed, stream, n)
+    s = np.zeros(n, np.int64)
+    for sh in (0, 16, 32, 48):
+        s += ((h >> np.uint64(sh)) & np.uint64(0xFFFF)).astype(np.int64)
+    return s - 131070
+
+
+def fa_case(name):
+    """the inputs of FA_CASES[name]: q f32 [T][H][D] (multiples of 2^-15, std 1.15 x q_amp: 18 significant bits, so
+    the kernel's own rounding of q to f16 is exercised), k f16 [n_kv][HKV][D] (amplitude 0.5: std 0.58), v f16 (std 1.15),
+    mask f16 [T][n_kv], crc = CRC32 of their bytes in that order, and the case's parameters"""
+    import zlib
+    c = dict(FA_CASES[name])
+    T, H, HKV, D, n_kv = (c[n] for n in ("T", "H", "HKV", "D", "n_kv"))
+    seed = zlib.crc32(name.encode())
+    q = (_hash_bell(seed, 1, T * H * D).astype(np.float64) * (c.get("q_amp", 1) / 32768.0)).astype(np.float32)
+    k = (_hash_bell(seed, 2, n_kv * HKV * D).astype(np.float64) / 65536.0).astype(np.float16)
+    v = (_hash_bell(seed, 3, n_kv * HKV * D).astype(np.float64) / 32768.0).astype(np.float16)
+    hm = _hash64(seed, 4, T * n_kv).reshape(T, n_kv)
+    mask = np.zeros((T, n_kv), np.float16)
+    if c.get("finite"):
+        mask = ((hm & np.uint64(0x7FF)).astype(np.float64) / -1024.0).astype(np.float16)     # exact f16 in (-2, 0]
+    if c.get("holes"):
+        mask[((hm >> np.uint64(32)) % np.uint64(5)) == 0] = -np.inf
+        c["n_past"] = None
+    else:
+        for t in range(T):
+            mask[t, c["n_past"] + t + 1:] = -np.inf
+    for lo, hi in c.get("dead", []):
+        mask[:, lo:hi] = -np.inf
+    assert np.all(np.isfinite(mask.astype(np.float32)).any(axis=1))      # every row keeps a live key
+    c.update(name=name, q=q.reshape(T, H, D), k=k.reshape(n_kv, HKV, D), v=v.reshape(n_kv, HKV, D), mask=mask)
+    c["crc"] = zlib.crc32(c["q"].tobytes() + c["k"].tobytes() + c["v"].tobytes() + mask.tobytes())
+    return c
 
 
 class HParams(ctypes.Structure):

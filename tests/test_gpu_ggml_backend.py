@@ -9,8 +9,9 @@ same graph computed by the reference CPU backend is the expected result.
 Bars: quantized and F16 mat-mul: exact integer dots, fp32 combination order only -> max |d| <= 3e-6 x max |ref|.
 Elementwise / norm / rope ops: 2e-6 relative.  A whole Llama layer (norm, q/k/v, rope, f16 KV-cache stores into
 cache views, masked flash attention over the cache, wo, residual, norm, gate/up/silu, down, residual): 2e-5
-with the strict-parity attention (kcpp_ggml_backend_set_fa_exact), 2e-2 with the production one (the reference
-accumulates attention in f16, ggml.c:15788, this backend in f32)."""
+with the strict-parity attention (kcpp_ggml_backend_set_fa_exact) while its inputs are bit-equal to the CPU run's
+(its FA node is held bit-equal to the reference's on the same inputs at every length), 2e-2 with the production
+one (the reference accumulates attention in f16, ggml.c:15788, this backend in f32)."""
 import ctypes
 import os
 
@@ -286,13 +287,42 @@ def test_llama_layer_vs_reference_cpu(env, exact, n_past, T, n_ctx, pad):
         out = G.ggml_add(ctx, G.ggml_mul_mat(ctx, W[6], h), ffn_in)
         # the cache stores must precede attention (llm_build_kv: ggml_build_forward_expand of the cpy nodes first)
         build.pre = [st_k, st_v]
+        build.keep = [q, KC, VC, fa]        # the attention node's inputs and output, read back in the strict mode
         return W + [N1, N2, X, KC, VC, Pz, Mk], out
 
     def inputs():
         return ws + [nw1, nw2, x, kc, vc, pos, mask]
 
+    def fa_only_cpu(qv, kcb, vcb):
+        """the reference CPU's ggml_flash_attn_ext alone, on the given q [T][H][D] f32 and cache bytes"""
+        ctx = G.ggml_init(InitParams(64 << 20, None, False))
+        Q = G.ggml_new_tensor_3d(ctx, R.F32, D, H, T)
+        KC, VC = G.ggml_new_tensor_1d(ctx, R.F16, n_ctx * EKV), G.ggml_new_tensor_1d(ctx, R.F16, n_ctx * EKV)
+        Mk = G.ggml_new_tensor_2d(ctx, R.F16, n_kv, T_pad)
+        for t, a in ((Q, qv), (KC, kcb), (VC, vcb), (Mk, mask)):
+            a = np.ascontiguousarray(a)
+            assert a.nbytes == G.ggml_nbytes(t)
+            ctypes.memmove(G.ggml_get_data(t), a.ctypes.data, a.nbytes)
+        kview = G.ggml_view_3d(ctx, KC, D, n_kv, HKV, EKV * 2, D * 2, 0)
+        vview = G.ggml_view_3d(ctx, VC, D, n_kv, HKV, EKV * 2, D * 2, 0)
+        fa = G.ggml_flash_attn_ext(ctx, G.ggml_permute(ctx, Q, 0, 2, 1, 3), kview, vview, Mk, 1.0 / np.sqrt(D), 0.0, 0.0)
+        g = G.ggml_new_graph(ctx)
+        G.ggml_build_forward_expand(g, fa)
+        assert G.ggml_graph_compute_with_ctx(ctx, g, 8) == 0
+        res = np.ctypeslib.as_array((ctypes.c_float * (T * H * D)).from_address(G.ggml_get_data(fa))).copy()
+        G.ggml_free(ctx)
+        return res
+
+    def grab(t, dtype, on_gpu):
+        a = np.empty(G.ggml_nbytes(t) // np.dtype(dtype).itemsize, dtype)
+        if on_gpu:
+            G.ggml_backend_tensor_get(t, a.ctypes.data, 0, a.nbytes)
+        else:
+            ctypes.memmove(a.ctypes.data, G.ggml_get_data(t), a.nbytes)
+        return a
+
     L.kcpp_ggml_backend_set_fa_exact(ctypes.c_void_p(be), int(exact))
-    outs = []
+    outs, kept = [], []
     for on_gpu in (True, False):
         ctx = G.ggml_init(InitParams(256 << 20, None, on_gpu))
         ins, out = build(ctx)
@@ -310,6 +340,10 @@ def test_llama_layer_vs_reference_cpu(env, exact, n_past, T, n_ctx, pad):
             assert G.ggml_backend_graph_compute(be, g) == 0, L.kcpp_ggml_backend_last_error()
             res = np.empty(T * E, np.float32)
             G.ggml_backend_tensor_get(out, res.ctypes.data, 0, res.nbytes)
+            # (ggml_backend_alloc_ctx_tensors gives every tensor its own memory, and a fused launch writes every
+            # node's output, the roped q included -- fuse_mv_rope -- so the readback needs no unfused run)
+            if exact:
+                kept.append([grab(t, dt, True) for t, dt in zip(build.keep, (np.float32, np.uint16, np.uint16, np.float32))])
             G.ggml_backend_buffer_free(buf)
         else:
             for t, a in zip(ins, inputs()):
@@ -317,16 +351,49 @@ def test_llama_layer_vs_reference_cpu(env, exact, n_past, T, n_ctx, pad):
                 ctypes.memmove(G.ggml_get_data(t), a.ctypes.data, a.nbytes)
             assert G.ggml_graph_compute_with_ctx(ctx, g, 8) == 0
             res = np.ctypeslib.as_array((ctypes.c_float * (T * E)).from_address(G.ggml_get_data(out))).copy()
+            if exact:
+                kept.append([grab(t, dt, False) for t, dt in zip(build.keep, (np.float32, np.uint16, np.uint16, np.float32))])
         G.ggml_free(ctx)
         outs.append(res)
     L.kcpp_ggml_backend_set_fa_exact(ctypes.c_void_p(be), 0)
     e = rel(outs[0], outs[1])
     med = float(np.median(np.abs(outs[0] - outs[1])) / np.abs(outs[1]).max())
     print("layer exact=%d rel err max %.3g median %.3g" % (exact, e, med))
-    # (the strict-order attention matches a layer to 2e-5 over tens of keys; over 700 keys its result drifts to 4e-3 of
-    # the reference's -- measured the same with and without this round's single-token paths -- so that case only
-    # proves the masked NaN cells stay out; the strict mode is pinned end to end at 3840 keys by test_gpu_deep.py)
-    assert e <= (LAYER_EXACT if exact and n_past < 100 else LAYER_PROD), e
+    n_flipped = 0
+    if exact:
+        (q_g, kc_g, vc_g, fa_g), (q_c, kc_c, vc_c, fa_c) = kept
+        # 1. the instrument: the strict kernel's FA node against the reference CPU's ggml_flash_attn_ext ALONE on the
+        # GPU run's own q, cache bytes and mask -- the op-level bar of test_gpu_fa_exact.py (bit-equal up to an exp tie)
+        fa_r = fa_only_cpu(q_g, kc_g, vc_g)
+        n_bits = int((fa_g.view(np.uint32) != fa_r.view(np.uint32)).sum())
+        print("FA node on the GPU run's inputs, %d keys: %d of %d outputs differ in any bit, max |d| %.3g" % (
+            n_past + T, n_bits, fa_g.size, np.abs(fa_g - fa_r).max()))
+        assert np.abs(fa_g - fa_r).max() <= np.spacing(np.abs(fa_r).max())
+        # 2. the inputs: f16 codes of q (as attention rounds it) and of the new cache rows that differ between the runs
+        rows = slice(n_past * EKV, (n_past + T) * EKV)
+        flips = [int((q_g.astype(np.float16).view(np.uint16) != q_c.astype(np.float16).view(np.uint16)).sum()),
+                 int((kc_g[rows] != kc_c[rows]).sum()), int((vc_g[rows] != vc_c[rows]).sum())]
+        n_flipped = sum(flips)
+        fa_e = rel(fa_g, fa_c)
+        n_q8 = int((R.quantize(R.Q8_K, fa_g) != R.quantize(R.Q8_K, fa_c)).sum())      # wo's activation (vec_dot_type)
+        print("attention inputs: %d f16 codes differ GPU vs CPU (q %d of %d, new K rows %d, new V rows %d of %d); "
+              "FA node GPU vs CPU run rel err %.3g, %d bytes of its Q8_K image differ" % (
+                  n_flipped, flips[0], q_g.size, flips[1], flips[2], T * EKV, fa_e, n_q8))
+        # rows the graph does not store must be the uploaded bytes on both sides
+        assert np.array_equal(kc_g[:rows.start], kc_c[:rows.start]) and np.array_equal(vc_g[:rows.start], vc_c[:rows.start])
+    # What the 700-key case's 3.99e-3 max / 8.7e-4 median is (measured): NOT the kernel -- the FA node is bit-equal
+    # to the reference CPU's on the same inputs at 38, 42 and 701 keys (0 differing bits, assertion 1.).  Its INPUTS
+    # differ: q and the new K row reach attention through a quantized mat-mul and RoPE that agree with the CPU only to
+    # ~3e-6, which flips f16 codes (2 at 701 keys: one in q, one in the new K row; 2 at 38 keys; 10 of 7680 at 42 keys,
+    # 5 rows).  The strict order is chaotic in its inputs -- one f16 ulp of q moves every output of the head, by ~1e-3
+    # of the head's maximum over 701 keys -- so the FA nodes of the two runs differ by 1.3e-4 ..
+    # 3.9e-4, and wo's Q8_K rounding of that activation (a flipped code is 1/127 of its block's maximum) and the FFN's
+    # two further activation roundings carry a difference of this class into the layer output, or do not: the same
+    # two flips leave the 38-key layer at 2.5e-7.  So the 2e-5 layer bar is a statement about bit-equal attention
+    # inputs: it holds whenever no code flipped, and below 100 keys as before; with flipped inputs assertion 1. carries
+    # the exactness claim and LAYER_PROD stays the sanity bound.  (The strict mode is also pinned end to end at 3840
+    # keys by test_gpu_deep.py.)
+    assert e <= (LAYER_EXACT if exact and (n_past < 100 or n_flipped == 0) else LAYER_PROD), e
 
 
 def test_unsupported_ops_are_refused(env):
