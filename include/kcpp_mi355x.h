@@ -72,10 +72,26 @@ int64_t kcpp_gemm_grouped_ws_bytes(int type, int64_t K, int64_t M, int ng);
 int kcpp_gemm_grouped(int type, const void *W, const void *W2, int64_t wstride, int64_t K, int64_t N, const void *act,
                       int64_t M, const int32_t *cnt_host, const int32_t *cnt_dev, int ng, float *Y, float *up, int mode,
                       void *ws, void *stream);
-/* Q4_K GEMM kernel generation for later kcpp_gemm calls: 3 (= 0, the default; env KCPP_GEMM_V) = 128(64) x 128
- * tiles, LDS-DMA activation, register-dequantized weights; 2 = 128(256) x 64 tiles, LDS weights.  Same results
- * bit for bit.  Returns the previous value. */
+/* Kernel choice of later kcpp_gemm / kcpp_gemm_grouped calls (tests and tools; the table is csrc/gemm_plan.h
+ * gemm_force_of).  0 (and any negative value) = the rules, the default.  Among the K-quant kernels (v2: 128(256) x 64
+ * tiles, LDS weights; v3 = q4v3 / q6v3: 128(64) x 128 tiles, LDS-DMA activation, register-dequantized weights;
+ * v4 / v5: int8 matrix cores) unsplit results are bit for bit the same; a K split changes the f32 summation order.
+ *    2  v2 for every K-quant                     3  v3 unsplit (Q6_K base layout: v2)
+ *    4  v3, K split in two wherever allowed      5  v3 unsplit, weights loaded two super-blocks ahead
+ *    6  as 5 with 4 waves                        7  v3 unsplit, 4 waves
+ *    8 / 9 / 10  v3 unsplit, XG 2 / 4 / 8 token tiles per XCD group
+ *   11  v4 wherever it can run (its split rule), else v3 unsplit        12  as 11 with XG 2
+ *   13  v4 unsplit, else v3 unsplit              14  v5 (Q5_K: v4), else v2
+ *   15 / 16 / 17  v3 with its split rule, q6v3's tile (BMT, waves) = (4, 4) / (4, 8) / (2, 8)
+ *   20  as 2, and the mat-vec path at every M for the types that have it (Q4_1, Q5_1, IQ4_NL, IQ4_XS, IQ1-3)
+ *   21  as 2, and v1 (every other type) unsplit
+ * Every other value behaves like 2.  Returns the previous value. */
 int kcpp_gemm_set_variant(int v);
+/* The plan kcpp_gemm would run for this shape under the current variant; host-only, launches nothing (K a multiple
+ * of 256; bs_aligned: the activation's Q8_K bsums sit on a 16-byte boundary).  out = {family, layout (1 = RS), tile
+ * (v2 TM / v3 BMT / v4 TPW), waves, KS, XG, PF, workgroups of one launch}; family: 0 mat-vec columns, 1 Q8_0 small
+ * batch, 2 v1, 3 v2, 4 q4v3, 5 q6v3, 6 v4 (csrc/gemm_plan.h).  -1 bad arguments, -3 a type kcpp_gemm plans elsewhere. */
+int kcpp_gemm_plan(int type, int64_t K, int64_t N, int64_t M, int mode, int bs_aligned, int32_t out[8]);
 /* Q8_0 at M <= 32 over nseg <= 3 weights whose outputs sit back to back in Y's columns (q|k|v of one layer,
  * one activation quantization and one launch instead of three); every N_i but the last a multiple of 128;
  * ws from kcpp_gemm_workspace_bytes(KT_Q8_0, K, sum N_i, M) */

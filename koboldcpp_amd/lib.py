@@ -122,6 +122,7 @@ _SIGS = {
     "kcpp_model_set_fused_decode": [P, I],
     "kcpp_model_set_row_split": [P, I, P, P],
     "kcpp_row_split_range": [I64, I, P, I, P, P],
+    "kcpp_gemm_plan": [I, I64, I64, I64, I, I, P],
     "kcpp_model_set_fa_exact": [P, I],
     "kcpp_model_set_rope_freqs": [P, P, I],
     "kcpp_gradient_ai_rope_base": [Fl, I, I, I],
@@ -439,6 +440,19 @@ def row_split_range(nrows, tensor_split, i):
     lo, hi = ctypes.c_int64(0), ctypes.c_int64(0)
     _chk(_L.kcpp_row_split_range(int(nrows), n, ts, int(i), ctypes.byref(lo), ctypes.byref(hi)), "row_split_range")
     return lo.value, hi.value
+
+
+GEMM_FAMILY = ("cols", "q80s", "v1", "v2", "q4v3", "q6v3", "v4")
+
+
+def gemm_plan(t, K, N, M, mode=0, bs_aligned=True):
+    """what kcpp_gemm would launch under the current variant (kcpp_gemm_plan; host only): dict of family (a
+    GEMM_FAMILY name), rs, tile (v2 TM / v3 BMT / v4 TPW), waves, ks, xg, pf, nwg"""
+    out = (ctypes.c_int32 * 8)()
+    _chk(_L.kcpp_gemm_plan(int(t), int(K), int(N), int(M), int(mode), int(bool(bs_aligned)), out), "gemm_plan")
+    d = dict(zip(("family", "rs", "tile", "waves", "ks", "xg", "pf", "nwg"), out))
+    d["family"] = GEMM_FAMILY[d["family"]]
+    return d
 
 
 def pipeline_trace(n_stages, ubatch, T, n_past, steps):

@@ -1,4 +1,4 @@
-"""Q6_K prefill image + int8-MFMA GEMM (kcpp_q6p_build / kcpp_gemm_q6p, csrc/gemm.hip k_gemm_q6p).
+"""Q6_K prefill image + int8-MFMA GEMM (kcpp_q6p_build / kcpp_gemm_q6p, csrc/gemm_q6p.hip k_gemm_q6p).
 
 The image holds each weight's exact integer sc*(q-32) as two int8 planes (64 A + C); the GEMM multiplies them with
 the Q8_K bytes on v_mfma_i32_32x32x32_i8 and applies q6v3's per-super-block epilogue in q6v3's order, under

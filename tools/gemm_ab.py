@@ -15,6 +15,7 @@ import koboldcpp_amd.lib as K  # noqa: E402
 
 def main():
     variants = [int(v) for v in sys.argv[1:]] or [2, 3]
+    torch.manual_seed(0)        # the same activations in every process: GEMM_DUMP files compare across builds
     s = torch.cuda.current_stream()
     sp = s.cuda_stream
     M = int(os.environ.get("GEMM_M", "512"))
