@@ -286,7 +286,9 @@ int kcpp_ggml_rope_f16(const void *x, const kcpp_tdesc *tx, void *y, const kcpp_
 int kcpp_ggml_rope(const void *x, const kcpp_tdesc *tx, void *y, const kcpp_tdesc *ty, const int32_t *pos,
                    const float *freq_factors, int n_dims, int mode, int n_ctx_orig, float freq_base, float freq_scale,
                    float ext_factor, float attn_factor, float beta_fast, float beta_slow, void *stream);
-/* softmax(x * scale + mask[row % mask_rows]) per row; mask KT_F16 / KT_F32 or null */
+/* softmax(x * scale + mask[row % mask_rows]) per row, row the flat row index over x's dims 1..3; mask KT_F16 / KT_F32
+ * or null.  mask_rows is x's (src0's) ne[1], ggml's rule (ggml.c:13965) -- NOT the mask's own row count, which
+ * llama.cpp pads to a multiple of 32 with rows of -inf; the mask holds at least that many rows of mask_ld elements */
 int kcpp_ggml_soft_max(const void *x, const kcpp_tdesc *tx, const void *mask, int mask_type, int64_t mask_ld,
                        int64_t mask_rows, void *y, const kcpp_tdesc *ty, float scale, void *stream);
 int kcpp_ggml_argsort(const void *x, const kcpp_tdesc *tx, int32_t *d, int64_t ld, int desc, void *stream);

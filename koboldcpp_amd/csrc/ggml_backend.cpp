@@ -607,9 +607,14 @@ bool supports(const kggml_tensor *op) {
         const int mode = op->op_params[2];
         return f32(op) && f32(op->src[0]) && (mode == 0 || mode == 2) && op->src[0]->nb[0] == 4;
     }
-    case KGGML_OP_SOFT_MAX:
-        return f32(op) && f32(op->src[0]) && op_f(op, 1) == 0.0f &&
-               (!op->src[1] || op->src[1]->type == KGGML_TYPE_F16 || op->src[1]->type == KGGML_TYPE_F32);
+    case KGGML_OP_SOFT_MAX: {
+        const kggml_tensor *a = op->src[0], *m = op->src[1];
+        if (!f32(op) || !f32(a) || op_f(op, 1) != 0.0f) return false;
+        // a mask of src0's row length with a row for each of src0's ne[1] (ggml_soft_max_impl's assertions): the
+        // kernel reads mask row (flat row % src0's ne[1])
+        return !m || ((m->type == KGGML_TYPE_F16 || m->type == KGGML_TYPE_F32) && m->ne[0] == a->ne[0] &&
+                      m->ne[1] >= a->ne[1]);
+    }
     case KGGML_OP_ARGSORT:
         return f32(op->src[0]) && op->type == KGGML_TYPE_I32;
     case KGGML_OP_SUM_ROWS:
@@ -894,7 +899,9 @@ bool compute_node(BackendCtx *bc, kggml_tensor *n) {
         const kggml_tensor *m = b;
         const int mt = m ? (m->type == KGGML_TYPE_F16 ? KT_F16 : KT_F32) : KT_F32;
         const int64_t mld = m ? (int64_t)(m->nb[1] / kTraits[m->type].size) : 0;
-        return chk(kcpp_ggml_soft_max(a->data, &ta, m ? m->data : nullptr, mt, mld, m ? m->ne[1] : 1, n->data, &td,
+        // the mask row of flat row r is r % src0's ne[1] (ggml.c:13965; softmax.cu: rowx % nrows_y), not r % the mask's
+        // own row count: llama.cpp pads the mask to 32 rows of -inf, which no head may read
+        return chk(kcpp_ggml_soft_max(a->data, &ta, m ? m->data : nullptr, mt, mld, a->ne[1], n->data, &td,
                                       op_f(n, 0), s),
                    "soft_max");
     }
@@ -923,9 +930,12 @@ bool compute_node(BackendCtx *bc, kggml_tensor *n) {
         if (a->buffer && buffer_is_split(a->buffer)) return mul_mat_split(bc, n);
         if (a->type == KGGML_TYPE_F32 || a->type == KGGML_TYPE_F16) {
             const kcpp_tdesc ta = td_of(a), tb = td_of(b);
-            // F16 weights: the reference CPU (AVX2/F16C build) hands contiguous f32 src1 with K % 8 == 0 to
-            // tinyBLAS unrounded (llamafile/sgemm.cpp:1094-1103), otherwise rounds src1 to f16 (vec_dot_f16)
-            const int wt = a->type == KGGML_TYPE_F16 && is_contiguous(b) && a->ne[0] % 8 == 0 ? KCPP_MM_F16_X32 : a->type;
+            // F16 weights: the reference CPU (AVX2/F16C build) hands contiguous f32 src1 of two or more columns with
+            // K % 8 == 0 to tinyBLAS unrounded (ggml.c:12540-12557, llamafile/sgemm.cpp:1094-1103); tinyBLAS refuses a
+            // single column (sgemm.cpp:1033, "only enable sgemm for prompt processing"), and then, as for any other
+            // src1, the reference rounds src1 to f16 (vec_dot_f16) -- the decode-time kqv product among them
+            const int wt = a->type == KGGML_TYPE_F16 && is_contiguous(b) && a->ne[0] % 8 == 0 && b->ne[1] >= 2
+                               ? KCPP_MM_F16_X32 : a->type;
             return chk(kcpp_ggml_mul_mat_f(wt, a->data, &ta, (const float *)b->data, &tb, (float *)n->data, &td, s),
                        "mul_mat_f");
         }

@@ -312,7 +312,8 @@ __global__ void k_rope(const char *__restrict__ x, TD tx, char *__restrict__ y, 
     }
 }
 
-// ---------------------------------------------------------------- soft_max (+ mask row i1 % mask_rows)
+// ---------------------------------------------------------------- soft_max (+ mask row r % mask_rows, r the flat row;
+// mask_rows = src0's ne[1], the caller's duty)
 template <bool MF16>
 __global__ void __launch_bounds__(256) k_soft_max(const char *__restrict__ x, TD tx, const void *__restrict__ mask,
                                                   int64_t mask_ld, int64_t mask_rows, char *__restrict__ y, TD ty,

@@ -97,6 +97,20 @@ def mul_mat(t, w, K, N, X, nthreads=0):
     return dst
 
 
+def mm_rounding_probe(rng, M, K, N):
+    """Inputs on which an F16 mul_mat with src1 rounded to f16 and one with src1 left in f32 give results far apart.
+    Weights are positive (0.025 .. 0.075).  src1 is +(1 + 2^-11 - 2^-20) -- which f16 rounds down to 1 -- on 9 of every
+    16 blocks of 64 columns and exactly -1 on the other 7 (odd rows negated): the blocks mostly cancel, so the rounded
+    result is ~1/8 of sum |w|, and the unrounded one carries ~2^-11 * 9/16 * sum |w| on top, ~2e-3 of the result, while
+    the condition number stays 8.  Returns w f16 [N][K], x f32 [M][K] and the fp64 results (rounded, unrounded)."""
+    w = (0.025 + 0.05 * rng.random((N, K))).astype(np.float16)
+    blk = np.arange(K) // 64 % 16
+    row = np.where((blk % 2 == 0) | (blk == 1), np.float32(1 + 2.0 ** -11 - 2.0 ** -20), np.float32(-1)).astype(np.float32)
+    x = np.stack([row if m % 2 == 0 else -row for m in range(M)])
+    w64 = w.astype(np.float64)
+    return w, x, x.astype(np.float16).astype(np.float64) @ w64.T, x.astype(np.float64) @ w64.T
+
+
 def rms_norm(x, w, eps):
     x = np.ascontiguousarray(x, dtype=np.float32)
     y = np.empty_like(x)

@@ -11,7 +11,9 @@ Elementwise / norm / rope ops: 2e-6 relative.  A whole Llama layer (norm, q/k/v,
 cache views, masked flash attention over the cache, wo, residual, norm, gate/up/silu, down, residual): 2e-5
 with the strict-parity attention (kcpp_ggml_backend_set_fa_exact) while its inputs are bit-equal to the CPU run's
 (its FA node is held bit-equal to the reference's on the same inputs at every length), 2e-2 with the production
-one (the reference accumulates attention in f16, ggml.c:15788, this backend in f32)."""
+one (the reference accumulates attention in f16, ggml.c:15788, this backend in f32).  The graph llama.cpp builds with
+flash attention OFF (koboldcpp's default: mul_mat / soft_max_ext / mul_mat over the K view and the transposed V
+cache, the transposed V store): the attention alone 7e-7, the whole layer 1.6e-6 (f32 attention on both sides)."""
 import ctypes
 import os
 
@@ -47,7 +49,8 @@ def env():
             "ggml_soft_max_ext": ([P, P, P, F, F], P),
             "ggml_rope_ext": ([P, P, P, P, I, I, I, F, F, F, F, F, F], P),
             "ggml_flash_attn_ext": ([P, P, P, P, P, F, F, F], P),
-            "ggml_view_1d": ([P, P, I64, SZ], P), "ggml_view_3d": ([P, P, I64, I64, I64, SZ, SZ, SZ], P),
+            "ggml_view_1d": ([P, P, I64, SZ], P), "ggml_view_2d": ([P, P, I64, I64, SZ, SZ], P),
+            "ggml_transpose": ([P, P], P), "ggml_cont_2d": ([P, P, I64, I64], P), "ggml_view_3d": ([P, P, I64, I64, I64, SZ, SZ, SZ], P),
             "ggml_reshape_2d": ([P, P, I64, I64], P), "ggml_reshape_3d": ([P, P, I64, I64, I64], P),
             "ggml_permute": ([P, P, I, I, I, I], P), "ggml_new_graph": ([P], P),
             "ggml_build_forward_expand": ([P, P], None), "ggml_graph_compute_with_ctx": ([P, P, I], I),
@@ -160,6 +163,7 @@ def test_registry_device_and_buffer_rules(env):
 MM_CASES = [(R.Q4_K, 4096, 512, 1), (R.Q4_K, 4096, 384, 7), (R.Q4_K, 2048, 256, 40), (R.Q6_K, 4096, 256, 1),
             (R.Q6_K, 2048, 256, 33), (R.Q5_K, 4096, 256, 1), (R.Q5_K, 2048, 128, 20), (R.Q8_0, 4096, 256, 1),
             (R.Q8_0, 2048, 256, 24), (R.Q4_0, 4096, 256, 1), (R.Q4_0, 2048, 256, 40), (R.F16, 1024, 96, 5),
+            (R.F16, 1024, 96, 1), (R.F16, 1024, 96, 2),
             (R.Q2_K, 4096, 256, 1), (R.Q2_K, 2048, 256, 24), (R.Q3_K, 4096, 256, 1), (R.Q3_K, 2048, 384, 40),
             (R.Q5_0, 4096, 256, 1), (R.Q5_0, 2048, 256, 24), (R.Q4_1, 4096, 256, 1), (R.Q4_1, 2048, 256, 24),
             (R.Q5_1, 4096, 256, 3), (R.Q5_1, 2048, 256, 40), (R.IQ4_NL, 4096, 256, 1), (R.IQ4_NL, 2048, 256, 24),
@@ -175,12 +179,21 @@ def test_mul_mat_vs_reference_cpu(env, case):
     rng = np.random.default_rng(Kd + N + M + t)
     w = R.synth(t, 5, 100 + t, Kd, N) if t != R.F16 else (rng.standard_normal((N, Kd)) * 0.05).astype(np.float16)
     x = rng.standard_normal((M, Kd)).astype(np.float32)
+    probe = t == R.F16 and M <= 2
+    if probe:
+        # F16 weights at one and two tokens: the reference rounds src1 to f16 at one token (vec_dot_f16: tinyBLAS
+        # refuses n < 2, llamafile/sgemm.cpp:1033) and leaves it in f32 from two on (tinyBLAS); on these inputs the two
+        # results lie more than 100 bars apart on every output, so the backend must pick the same route
+        w, x, want_r, want_u = R.mm_rounding_probe(rng, M, Kd, N)
+        assert np.abs(want_r - want_u).min() >= 100 * 3e-6 * max(np.abs(want_r).max(), np.abs(want_u).max())
 
     def build(ctx):
         W = G.ggml_new_tensor_2d(ctx, t, Kd, N)
         X = G.ggml_new_tensor_2d(ctx, R.F32, Kd, M)
         return [W, X], G.ggml_mul_mat(ctx, W, X)
     ours, ref = run_both(G, be, build, lambda: [w, x])
+    if probe:
+        assert rel(ref, (want_r if M == 1 else want_u).ravel()) <= 3e-6       # the route the reference took
     assert rel(ours, ref) <= 3e-6, rel(ours, ref)
     assert L.kcpp_ggml_backend_last_nodes() == 1
 
@@ -601,6 +614,177 @@ def test_llama_layer_variants_vs_reference_cpu(env, case):
 
 
 LAYER_KVQ = 1e-2
+
+
+# ---- attention WITHOUT flash attention: koboldcpp's default (no --flashattention), llm_build_kqv's else branch
+def nofa_attention(G, ctx, q_cur, KC, VC, Mk, H, HKV, D, T, n_kv, n_ctx):
+    """llm_build_kqv without flash attention (src/llama.cpp:9543-9628) on q_cur f32 [D, H, T], the K cache f16
+    [n_ctx][HKV * D] and the TRANSPOSED V cache f16 [HKV * D][n_ctx]: kqv_merged_cont f32 [D * H, T]"""
+    EKV = HKV * D
+    q = G.ggml_permute(ctx, q_cur, 0, 2, 1, 3)
+    k = G.ggml_view_3d(ctx, KC, D, n_kv, HKV, EKV * 2, D * 2, 0)
+    kq = G.ggml_mul_mat(ctx, k, q)
+    kq = G.ggml_soft_max_ext(ctx, kq, Mk, 1.0 / np.sqrt(D), 0.0)
+    v = G.ggml_view_3d(ctx, VC, n_kv, D, HKV, n_ctx * 2, n_ctx * D * 2, 0)
+    kqv = G.ggml_mul_mat(ctx, v, kq)
+    return G.ggml_cont_2d(ctx, G.ggml_permute(ctx, kqv, 0, 2, 1, 3), D * H, T)
+
+
+def nofa_mask(T, n_past, n_kv):
+    """llama.cpp's KQ_mask without flash attention (src/llama.cpp:10293, filled at :16660-16703): F32
+    [n_kv, PAD(T, 32)], 0 inside the causal window, -inf elsewhere -- the cells from n_past + T to n_kv and every padded
+    row included -- and one hole inside the last token's window"""
+    mask = np.full(((T + 31) // 32 * 32, n_kv), -np.inf, np.float32)
+    for t in range(T):
+        mask[t, :n_past + t + 1] = 0
+    mask[T - 1, 1] = -np.inf
+    return mask
+
+
+# attention sub-graph vs the reference CPU: both sides round q (and, at one token, the probabilities) to f16 alike and
+# accumulate in f32, in different orders (measured 5.8e-8, 1.6e-7, 1.8e-7, 1.8e-7 over the four cases; before the mask
+# row and the one-token rounding were put right: NaN in three of them)
+ATTN_NOFA = 7e-7
+
+ATTN_NOFA_CASES = [(8, 2, 128, 1, 41, 64, 64), (8, 2, 128, 5, 37, 64, 64), (16, 4, 64, 33, 0, 64, 96),
+                   (4, 4, 128, 32, 10, 64, 64)]
+
+
+@pytest.mark.parametrize("case", ATTN_NOFA_CASES, ids=lambda c: "H%d_HKV%d_D%d_T%d_past%d_kv%d_ctx%d" % c)
+def test_attention_without_flash_attn_vs_reference_cpu(env, case):
+    """the attention of the graph llama.cpp builds when flash attention is off: mul_mat of the K-cache view with the
+    permuted q, soft_max_ext under the F32 mask padded to 32 rows, mul_mat of the transposed-V-cache view with the
+    probabilities, permute + cont_2d.  One token (the padded mask rows must stay unread: ggml takes mask row
+    flat_row % T, ggml.c:13965; and the probabilities are rounded to f16 as the reference's vec_dot_f16 route does),
+    5 tokens with 4 q heads per K / V head, 33 tokens (a second block of 32 mask rows, D = 64, V's row stride n_ctx
+    longer than n_kv) and exactly 32 tokens (the one count where the mask's row count and T coincide).  Cache cells no
+    query may see hold ordinary finite values: reading one moves the result."""
+    G, L, be = env
+    H, HKV, D, T, n_past, n_kv, n_ctx = case
+    EKV = HKV * D
+    rng = np.random.default_rng(H + D + T)
+    q = rng.standard_normal((T, H, D)).astype(np.float32)
+    kc = (rng.standard_normal((n_ctx, EKV)) * 0.5).astype(np.float16)
+    vc = rng.standard_normal((EKV, n_ctx)).astype(np.float16)
+    mask = nofa_mask(T, n_past, n_kv)
+
+    def build(ctx):
+        Q = G.ggml_new_tensor_3d(ctx, R.F32, D, H, T)
+        KC, VC = G.ggml_new_tensor_1d(ctx, R.F16, n_ctx * EKV), G.ggml_new_tensor_1d(ctx, R.F16, n_ctx * EKV)
+        Mk = G.ggml_new_tensor_2d(ctx, R.F32, n_kv, mask.shape[0])
+        return [Q, KC, VC, Mk], nofa_attention(G, ctx, Q, KC, VC, Mk, H, HKV, D, T, n_kv, n_ctx)
+    ours, ref = run_both(G, be, build, lambda: [q, kc, vc, mask])
+    assert np.isfinite(ref).all()
+    e = rel(ours, ref)
+    print("attention without flash attention %s: rel err max %.3g" % (case, e))
+    assert np.isfinite(ours).all(), "%d of %d outputs are not finite" % ((~np.isfinite(ours)).sum(), ours.size)
+    assert e <= ATTN_NOFA, e
+
+
+# whole layer without flash attention vs the reference CPU: the attention is f32 on both sides here, so only the fp32
+# combination order of the quantized dots remains, well inside LAYER_EXACT (measured 4.0e-7, 1.3e-7, 2.3e-7 over the
+# three cases; 0.36, 0.13, 0.26 before the fixes).  The T stored V columns, as f32, against the reference's: the v
+# mat-mul's one-ulp f32 differences move an f16 code here and there (measured 2.0e-6, 2.2e-6, 6.4e-5: one code of 1280,
+# 256 and 256 differs, by one f16 ulp)
+LAYER_NOFA = 1.6e-6
+VSTORE_NOFA = 2.5e-4
+
+# (the third case: one token on a weight layout whose mat-vec fuses the cache store -- a transposed single-token v is
+# contiguous by ggml's rule, its strided destination is not, so the V store must run as a plain CPY)
+LAYER_NOFA_CASES = [("nofa_d128", 1024, 8, 2, 128, R.Q4_K, 5, 37), ("nofa_d64_decode", 1024, 16, 4, 64, R.Q4_0, 1, 41),
+                    ("nofa_d128_decode", 1024, 8, 2, 128, R.Q4_K, 1, 41)]
+
+
+@pytest.mark.parametrize("case", LAYER_NOFA_CASES, ids=lambda c: c[0])
+def test_llama_layer_without_flash_attn_vs_reference_cpu(env, case):
+    """one build_llama layer as llama.cpp builds it with flash attention off: K stored through ggml_view_1d, V stored
+    TRANSPOSED (llm_build_kv_store: cpy(transpose(v_cur), view_2d(v_cache, T, n_embd_v_gqa, n_ctx * 2, kv_head * 2))),
+    attention from mul_mat / soft_max_ext / mul_mat / permute / cont_2d nodes.  Every node supported by this backend,
+    the output equal to the reference CPU backend's; the V cache afterwards holds the T new columns and, everywhere
+    else, the uploaded bytes."""
+    G, L, be = env
+    name, E, H, HKV, D, wt, T, n_past = case
+    Fd, n_ctx, n_kv = 2816, 64, 64
+    EKV = HKV * D
+    rng = np.random.default_rng(len(name))
+    shapes = [(E, E), (E, EKV), (E, EKV), (E, E), (E, Fd), (E, Fd), (Fd, E)]
+    ws = [R.synth(wt, 9, 300 + i, k, n) for i, (k, n) in enumerate(shapes)]
+    nw1 = (1 + 0.05 * rng.standard_normal(E)).astype(np.float32)
+    nw2 = (1 + 0.05 * rng.standard_normal(E)).astype(np.float32)
+    x = rng.standard_normal((T, E)).astype(np.float32)
+    kc = (rng.standard_normal((n_ctx, EKV)) * 0.5).astype(np.float16)
+    vc = rng.standard_normal((EKV, n_ctx)).astype(np.float16)
+    pos = np.arange(n_past, n_past + T, dtype=np.int32)
+    mask = nofa_mask(T, n_past, n_kv)
+    data = ws + [nw1, nw2, x, kc, vc, pos, mask]
+
+    def build(ctx):
+        W = [G.ggml_new_tensor_2d(ctx, wt, k, n) for k, n in shapes]
+        N1, N2 = G.ggml_new_tensor_1d(ctx, R.F32, E), G.ggml_new_tensor_1d(ctx, R.F32, E)
+        X = G.ggml_new_tensor_2d(ctx, R.F32, E, T)
+        KC, VC = G.ggml_new_tensor_1d(ctx, R.F16, n_ctx * EKV), G.ggml_new_tensor_1d(ctx, R.F16, n_ctx * EKV)
+        Pz = G.ggml_new_tensor_1d(ctx, 26, T)
+        Mk = G.ggml_new_tensor_2d(ctx, R.F32, n_kv, mask.shape[0])
+        cur = G.ggml_mul(ctx, G.ggml_rms_norm(ctx, X, 1e-5), N1)
+        q = G.ggml_rope_ext(ctx, G.ggml_reshape_3d(ctx, G.ggml_mul_mat(ctx, W[0], cur), D, H, T), Pz, None, D, 0, n_ctx,
+                            10000.0, 1.0, 0.0, 1.0, 32.0, 1.0)
+        k = G.ggml_rope_ext(ctx, G.ggml_reshape_3d(ctx, G.ggml_mul_mat(ctx, W[1], cur), D, HKV, T), Pz, None, D, 0, n_ctx,
+                            10000.0, 1.0, 0.0, 1.0, 32.0, 1.0)
+        v = G.ggml_mul_mat(ctx, W[2], cur)
+        st_k = G.ggml_cpy(ctx, k, G.ggml_view_1d(ctx, KC, T * EKV, n_past * EKV * 2))
+        st_v = G.ggml_cpy(ctx, G.ggml_transpose(ctx, v), G.ggml_view_2d(ctx, VC, T, EKV, n_ctx * 2, n_past * 2))
+        att = nofa_attention(G, ctx, q, KC, VC, Mk, H, HKV, D, T, n_kv, n_ctx)
+        att = G.ggml_mul_mat(ctx, W[3], att)
+        ffn_in = G.ggml_add(ctx, att, X)
+        h = G.ggml_mul(ctx, G.ggml_rms_norm(ctx, ffn_in, 1e-5), N2)
+        h = G.ggml_mul(ctx, G.ggml_silu(ctx, G.ggml_mul_mat(ctx, W[4], h)), G.ggml_mul_mat(ctx, W[5], h))
+        out = G.ggml_add(ctx, G.ggml_mul_mat(ctx, W[6], h), ffn_in)
+        return W + [N1, N2, X, KC, VC, Pz, Mk], out, [st_k, st_v], VC
+
+    outs, vcs = [], []
+    for on_gpu in (True, False):
+        ctx = G.ggml_init(InitParams(256 << 20, None, on_gpu))
+        ins, out, pre, VC = build(ctx)
+        g = G.ggml_new_graph(ctx)
+        for p_ in pre:      # the cache stores precede attention (llm_build_kv expands the cpy nodes first)
+            G.ggml_build_forward_expand(g, p_)
+        G.ggml_build_forward_expand(g, out)
+        res, vres = np.empty(T * E, np.float32), np.empty((EKV, n_ctx), np.float16)
+        if on_gpu:
+            bad = [i for i in range(G.ggml_graph_n_nodes(g)) if not G.ggml_backend_supports_op(be, G.ggml_graph_node(g, i))]
+            assert not bad, bad
+            buf = G.ggml_backend_alloc_ctx_tensors(ctx, be)
+            for t, a in zip(ins, data):
+                a = np.ascontiguousarray(a)
+                assert a.nbytes == G.ggml_nbytes(t)
+                G.ggml_backend_tensor_set(t, a.ctypes.data, 0, a.nbytes)
+            assert G.ggml_backend_graph_compute(be, g) == 0, L.kcpp_ggml_backend_last_error()
+            G.ggml_backend_tensor_get(out, res.ctypes.data, 0, res.nbytes)
+            G.ggml_backend_tensor_get(VC, vres.ctypes.data, 0, vres.nbytes)
+            G.ggml_backend_buffer_free(buf)
+        else:
+            for t, a in zip(ins, data):
+                a = np.ascontiguousarray(a)
+                ctypes.memmove(G.ggml_get_data(t), a.ctypes.data, a.nbytes)
+            assert G.ggml_graph_compute_with_ctx(ctx, g, 8) == 0
+            ctypes.memmove(res.ctypes.data, G.ggml_get_data(out), res.nbytes)
+            ctypes.memmove(vres.ctypes.data, G.ggml_get_data(VC), vres.nbytes)
+        G.ggml_free(ctx)
+        outs.append(res)
+        vcs.append(vres)
+    cols = slice(n_past, n_past + T)
+    for vres in vcs:        # every byte outside the T new columns is the uploaded one, on both sides
+        kept = vres.copy()
+        kept[:, cols] = vc[:, cols]
+        assert np.array_equal(kept.view(np.uint16), vc.view(np.uint16))
+    assert not np.array_equal(vcs[1][:, cols].view(np.uint16), vc[:, cols].view(np.uint16))   # the store happened
+    ev = rel(vcs[0][:, cols].astype(np.float32), vcs[1][:, cols].astype(np.float32))
+    n_codes = int((vcs[0][:, cols].view(np.uint16) != vcs[1][:, cols].view(np.uint16)).sum())
+    e = rel(outs[0], outs[1])
+    print("%s rel err max %.3g; stored V columns rel err max %.3g, %d of %d f16 codes differ" % (name, e, ev, n_codes,
+                                                                                              T * EKV))
+    assert ev <= VSTORE_NOFA, ev
+    assert e <= LAYER_NOFA, e
 
 
 @pytest.mark.parametrize("kvt", [R.Q8_0, R.Q4_0])

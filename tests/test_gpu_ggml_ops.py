@@ -172,6 +172,38 @@ def test_soft_max(env, mask):
     np.testing.assert_allclose(y.cpu().numpy(), e / e.sum(-1, keepdims=True), rtol=2e-6, atol=1e-9)
 
 
+@pytest.mark.parametrize("ne0", [300, 4])
+@pytest.mark.parametrize("mask", ["f16", "f32"])
+def test_soft_max_ggml_mask_rule(env, mask, ne0):
+    """ggml's mask rule (ggml.c:13965): the mask row of flat row r is r % src0.ne[1] -- the token, whatever the head or
+    batch -- and NOT r % (the mask's own row count): llama.cpp pads the mask to 32 rows of -inf (llama.cpp:10293), so
+    with T = 5 a kernel that wraps at 32 reads token rows for the wrong tokens and all -inf rows (sum 0 -> NaN).
+    The entry is called as the backend calls it: mask_rows = src0's ne[1].  Row lengths 300 (more than one pass of
+    the 256 threads) and 4 (a router-sized row, most threads idle).  In place (y is x, as ggml-alloc runs SOFT_MAX)
+    must give the out-of-place bits."""
+    torch, K = env
+    NE3, H, T, PAD = 2, 3, 5, 32
+    rng = np.random.default_rng(40 + ne0)
+    x = rng.standard_normal((NE3, H, T, ne0)).astype(np.float32)
+    m = np.full((PAD, ne0), -np.inf, np.float32)
+    m[:T] = np.where(rng.random((T, ne0)) < 0.3, -np.inf, rng.standard_normal((T, ne0)))
+    m[:T, 0] = 0.0
+    mh = m.astype(np.float16 if mask == "f16" else np.float32)
+    xd = torch.from_numpy(x).cuda()
+    md = torch.from_numpy(mh).cuda()
+    y = torch.full_like(xd, float("nan"))
+    mt = 1 if mask == "f16" else 0
+    run(torch, K, "kcpp_ggml_soft_max", xd, ("desc", xd), md, mt, ne0, T, y, ("desc", y), 0.5)
+    flat = np.arange(NE3 * H * T).reshape(NE3, H, T)
+    w = x.astype(np.float64) * 0.5 + mh.astype(np.float64)[flat % T]
+    e = np.exp(w - w.max(-1, keepdims=True))
+    got = y.cpu().numpy()
+    assert np.isfinite(got).all()
+    np.testing.assert_allclose(got, e / e.sum(-1, keepdims=True), rtol=2e-6, atol=1e-9)
+    run(torch, K, "kcpp_ggml_soft_max", xd, ("desc", xd), md, mt, ne0, T, xd, ("desc", xd), 0.5)
+    assert np.array_equal(xd.cpu().numpy().view(np.uint32), got.view(np.uint32))
+
+
 def _exchange_argsort(row, desc):
     idx = list(range(len(row)))
     for j in range(len(row)):
@@ -208,6 +240,135 @@ def test_mul_mat_f(env, wt):
     xr = x.astype(np.float16).astype(np.float64) if wt == R.F16 else x.astype(np.float64)
     want = np.stack([xr[b] @ w[b // 2].astype(np.float64).T for b in range(4)])
     np.testing.assert_allclose(d.cpu().numpy(), want, rtol=1e-5, atol=1e-5)
+
+
+MM_F16_X32 = 0x101      # KCPP_MM_F16_X32 (include/kcpp_mi355x.h): F16 weight x f32 src1 left unrounded
+
+
+def _mm_f(torch, K, mode, wd, xd, dshape):
+    d = torch.full(dshape, float("nan"), device="cuda")
+    run(torch, K, "kcpp_ggml_mul_mat_f", mode, wd, ("desc", wd), xd, ("desc", xd), d, ("desc", d))
+    return d.cpu().numpy()
+
+
+def _x64(x, mode):
+    """src1 as the mode's dot sees it, in fp64: rounded to f16 (KT_F16) or as it is (KCPP_MM_F16_X32)"""
+    return (x.astype(np.float16) if mode == R.F16 else x).astype(np.float64)
+
+
+def test_mul_mat_f_kq_views(env):
+    """the kq product of the graph without flash attention (llm_build_kqv, llama.cpp:9543-9578): src0 the f16 K-cache
+    view [D, n_kv, HKV] (row stride the whole cache row, head stride D), src1 the permuted q [D, T, H] -- not
+    contiguous, so the reference rounds it to f16 -- with 4 q heads per K head"""
+    torch, K = env
+    D, T, H, HKV, n_kv, n_ctx = 128, 3, 8, 2, 40, 48
+    rng = np.random.default_rng(21)
+    kc = (0.5 * rng.standard_normal((n_ctx, HKV * D))).astype(np.float16)
+    q = rng.standard_normal((T, H, D)).astype(np.float32)
+    wd = torch.from_numpy(kc).cuda()[:n_kv].view(n_kv, HKV, D).permute(1, 0, 2)        # ggml [D, n_kv, HKV]
+    xd = torch.from_numpy(q).cuda().permute(1, 0, 2)                                   # ggml [D, T, H]
+    assert not wd.is_contiguous() and not xd.is_contiguous()
+    got = _mm_f(torch, K, R.F16, wd, xd, (H, T, n_kv))
+    xr = _x64(q, R.F16)
+    k64 = kc[:n_kv].astype(np.float64).reshape(n_kv, HKV, D)
+    want = np.stack([xr[:, h] @ k64[:, h // (H // HKV)].T for h in range(H)])
+    np.testing.assert_allclose(got, want, rtol=1e-5, atol=1e-5)
+
+
+@pytest.mark.parametrize("mode,T", [(MM_F16_X32, 3), (R.F16, 1)], ids=["x32_T3", "f16_T1"])
+def test_mul_mat_f_kqv_views(env, mode, T):
+    """the kqv product: src0 the f16 view [n_kv, D, HKV] of llama's TRANSPOSED V cache [HKV * D][n_ctx] (row stride
+    n_ctx != n_kv), src1 the contiguous probabilities [n_kv, T, H]; unrounded src1 at T = 3 (the reference's tinyBLAS
+    route), f16-rounded at T = 1 (its vec_dot_f16 route: tinyBLAS refuses one column, sgemm.cpp:1033)"""
+    torch, K = env
+    D, H, HKV, n_kv, n_ctx = 64, 8, 2, 40, 48
+    rng = np.random.default_rng(22 + T)
+    vt = rng.standard_normal((HKV * D, n_ctx)).astype(np.float16)
+    p = rng.random((H, T, n_kv)).astype(np.float32)
+    p /= p.sum(-1, keepdims=True)
+    wd = torch.from_numpy(vt).cuda().view(HKV, D, n_ctx)[:, :, :n_kv]                  # ggml [n_kv, D, HKV]
+    xd = torch.from_numpy(p).cuda()
+    assert not wd.is_contiguous()
+    got = _mm_f(torch, K, mode, wd, xd, (H, T, D))
+    v64 = vt.astype(np.float64).reshape(HKV, D, n_ctx)[:, :, :n_kv]
+    want = np.stack([_x64(p[h], mode) @ v64[h // (H // HKV)].T for h in range(H)])
+    np.testing.assert_allclose(got, want, rtol=1e-5, atol=1e-5)
+
+
+@pytest.mark.parametrize("mode", [R.F16, MM_F16_X32], ids=["f16", "x32"])
+def test_mul_mat_f_broadcast_dim3(env, mode):
+    """src1 with ne3 = 2 over a src0 with ne3 = 1 (and 2 src1 heads per src0 head in dim 2)"""
+    torch, K = env
+    rng = np.random.default_rng(23)
+    w = (0.05 * rng.standard_normal((2, 24, 64))).astype(np.float16)
+    x = rng.standard_normal((2, 4, 3, 64)).astype(np.float32)
+    got = _mm_f(torch, K, mode, torch.from_numpy(w).cuda(), torch.from_numpy(x).cuda(), (2, 4, 3, 24))
+    xr = _x64(x, mode)
+    want = np.stack([np.stack([xr[b, h] @ w[h // 2].astype(np.float64).T for h in range(4)]) for b in range(2)])
+    np.testing.assert_allclose(got, want, rtol=1e-5, atol=1e-5)
+
+
+def rounding_probe_gap(M):
+    """the probe of refharness.mm_rounding_probe at [M] x 1024 x 96 and the smallest distance of its two fp64
+    expectations over all outputs, in units of test_mul_mat_f's tolerance (rtol = atol = 1e-5)"""
+    w, x, want_r, want_u = R.mm_rounding_probe(np.random.default_rng(24), M, 1024, 96)
+    tol = 1e-5 + 1e-5 * np.maximum(np.abs(want_r), np.abs(want_u))
+    return w, x, want_r, want_u, float((np.abs(want_r - want_u) / tol).min())
+
+
+@pytest.mark.parametrize("M", [1, 2])
+def test_mul_mat_f_rounding_mode_is_visible(env, M):
+    """KT_F16 rounds src1 to f16, KCPP_MM_F16_X32 does not: on the probe the two fp64 expectations lie at least 100
+    tolerances apart on every output (asserted here, on the CPU side), so a kernel running the other mode -- or a
+    tolerance too loose to tell them apart -- fails"""
+    torch, K = env
+    w, x, want_r, want_u, gap = rounding_probe_gap(M)
+    assert gap >= 100, gap
+    wd, xd = torch.from_numpy(w).cuda(), torch.from_numpy(x).cuda()
+    np.testing.assert_allclose(_mm_f(torch, K, R.F16, wd, xd, (M, 96)), want_r, rtol=1e-5, atol=1e-5)
+    np.testing.assert_allclose(_mm_f(torch, K, MM_F16_X32, wd, xd, (M, 96)), want_u, rtol=1e-5, atol=1e-5)
+
+
+def test_cpy_transposed_store_into_cache_view(env):
+    """the V store without flash attention (llm_build_kv_store, llama.cpp:9192-9202): transposed f32 v_cur
+    [T, E] (nb0 = E * 4, nb1 = 4) into the f16 view [T, E] of the transposed cache [E][n_ctx] at column 7: the stored
+    values are the f16 roundings, every other cache element keeps its bytes"""
+    torch, K = env
+    T, E, n_ctx, col = 5, 256, 20, 7
+    rng = np.random.default_rng(31)
+    v = rng.standard_normal((T, E)).astype(np.float32)
+    cache = rng.standard_normal((E, n_ctx)).astype(np.float16)
+    src = torch.from_numpy(v).cuda().t()                              # ggml ne [T, E], nb [E * 4, 4]
+    cd = torch.from_numpy(cache).cuda()
+    view = cd[:, col:col + T]                                         # ggml ne [T, E], nb [2, n_ctx * 2]
+    run(torch, K, "kcpp_ggml_cpy", 0, src, ("desc", src), 1, view, ("desc", view))
+    want = cache.copy()
+    want[:, col:col + T] = v.T.astype(np.float16)
+    assert np.array_equal(cd.cpu().numpy().view(np.uint16), want.view(np.uint16))
+
+
+def test_cpy_non_contiguous_sources(env):
+    """permuted f32 [D, H, T] (a view of [H][T][D]) into a contiguous [D * H, T] -- the kqv_merged_cont node: another
+    shape, so the element-order path, from a non-contiguous source; f16 -> f16 from a transposed source; f32 -> f32
+    from a source with an element stride of 8 bytes.  All bit for bit."""
+    torch, K = env
+    D, H, T = 64, 4, 5
+    rng = np.random.default_rng(32)
+    a = rng.standard_normal((H, T, D)).astype(np.float32)
+    src = torch.from_numpy(a).cuda().permute(1, 0, 2)                 # ggml ne [D, H, T]
+    dst = torch.full((T, D * H), float("nan"), device="cuda")
+    run(torch, K, "kcpp_ggml_cpy", 0, src, ("desc", src), 0, dst, ("desc", dst))
+    assert np.array_equal(dst.cpu().numpy().view(np.uint32), a.transpose(1, 0, 2).reshape(T, D * H).view(np.uint32))
+    h = rng.standard_normal((7, 33)).astype(np.float16)
+    src = torch.from_numpy(h).cuda().t()
+    dst = torch.zeros((33, 7), dtype=torch.float16, device="cuda")
+    run(torch, K, "kcpp_ggml_cpy", 1, src, ("desc", src), 1, dst, ("desc", dst))
+    assert np.array_equal(dst.cpu().numpy().view(np.uint16), np.ascontiguousarray(h.T).view(np.uint16))
+    f = rng.standard_normal((6, 70)).astype(np.float32)
+    src = torch.from_numpy(f).cuda()[:, ::2]
+    dst = torch.full((6, 35), float("nan"), device="cuda")
+    run(torch, K, "kcpp_ggml_cpy", 0, src, ("desc", src), 0, dst, ("desc", dst))
+    assert np.array_equal(dst.cpu().numpy().view(np.uint32), np.ascontiguousarray(f[:, ::2]).view(np.uint32))
 
 
 def _fa_ext(torch, K, q, k, v, mask, scale):
