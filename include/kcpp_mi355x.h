@@ -175,6 +175,15 @@ int kcpp_kv_shift_rows(const uint16_t *kc, const uint16_t *vc, uint16_t *ks, uin
                        const float *cs, void *stream);
 int kcpp_rope_kv(const float *qkv, int64_t ldqkv, float *q_out, uint16_t *q16, uint16_t *kc, uint16_t *vc, int T,
                  int H, int HKV, int D, int n_past, const int32_t *pos_dev, const void *rope_tab, void *stream);
+/* the same with a rope mode (ggml's values: 0 = NORM, pairs (2i, 2i+1); 2 = NeoX, pairs (i, i + D/2) inside a head)
+ * and optional f32 biases bq [H D], bk / bv [HKV D] added to the q / k / v rows first (build_qwen2's ggml_add in front
+ * of ggml_rope_ext, src/llama.cpp:12136-12246).  kcpp_rope_kv is mode 0 with null biases.  -1: another mode. */
+int kcpp_rope_kv_ex(const float *qkv, int64_t ldqkv, float *q_out, uint16_t *q16, uint16_t *kc, uint16_t *vc, int T,
+                    int H, int HKV, int D, int n_past, const int32_t *pos_dev, const void *rope_tab, int mode,
+                    const float *bq, const float *bk, const float *bv, void *stream);
+/* kcpp_kv_shift_rows with a rope mode (2: the K re-rotation on NeoX pairs, ggml_compute_forward_rope_f16) */
+int kcpp_kv_shift_rows_ex(const uint16_t *kc, const uint16_t *vc, uint16_t *ks, uint16_t *vs, int64_t rows, int D,
+                          const float *cs, int mode, void *stream);
 /* flash attention over the f16 cache (ggml_cuda_flash_attn_ext, fattn.cu:298-345) */
 /* force_path: 0 auto, 1 decode (T = 1: k_fa_dec4 splits + k_fa_comb4), 2 FMA-tiled prefill, 3 MFMA prefill
  * (D = 128, H = 4 HKV), 6 decode through the 64-key chunked kernel even at T = 1 */
@@ -198,6 +207,11 @@ int64_t kcpp_kv_cache_bytes(int type, int64_t n_ctx, int64_t ekv);
 /* RoPE (mode NORM, table as kcpp_rope_table) of the q and k heads in place in f32 q|k|v rows (stride ld) */
 int kcpp_rope_qk_inplace(float *qkv, int64_t ld, int T, int H, int HKV, int D, int n_past, const int32_t *pos_dev,
                          const void *rope_tab, void *stream);
+/* the same with a rope mode and biases (see kcpp_rope_kv_ex; the f32 results of the two agree bit for bit); bv is
+ * added to the v rows in place, where kcpp_kv_store_q reads them */
+int kcpp_rope_qk_inplace_ex(float *qkv, int64_t ld, int T, int H, int HKV, int D, int n_past, const int32_t *pos_dev,
+                            const void *rope_tab, int mode, const float *bq, const float *bk, const float *bv,
+                            void *stream);
 /* K (column koff) and V (column voff) of T f32 rows into the quantized caches at n_past + t (pos_dev[0] + t when
  * given): quantize_row_q8_0 (AVX2 rounding) / quantize_row_q4_0_ref, ggml-quants.c */
 int kcpp_kv_store_q(int tk, int tv, const float *qkv, int64_t ld, int64_t koff, int64_t voff, int T, int64_t ekv,
@@ -402,6 +416,14 @@ int kcpp_model_kv_shift(kcpp_model *m, int p0, int diff, int n_past);
  * the model and the context-shift K re-rotation divide the angle by them, as ggml_rope_ext with its freq_factors
  * operand (src/llama.cpp:7171, 10269, 10490; ggml.c ggml_rope_cache_init).  Rebuilds the rope table; synchronous. */
 int kcpp_model_set_rope_freqs(kcpp_model *m, const float *freq_factors, int n);
+/* rope mode of every rope of the model and of the context-shift K re-rotation: 0 = NORM (the default, Llama), 2 = NeoX
+ * (Qwen2: llama_rope_type, src/llama.cpp:19731); anything else returns -1.  Drops captured decode graphs. */
+int kcpp_model_set_rope_mode(kcpp_model *m, int mode);
+/* q / k / v projection biases of layer il (blk.N.attn_{q,k,v}.bias of a Qwen2 GGUF): host f32 arrays of n_embd,
+ * n_embd_gqa and n_embd_gqa values, added to the products before the rope (build_qwen2).  All three null clears the
+ * layer's bias; otherwise all three are required.  il must be a layer this stage owns.  Synchronous; drops captured
+ * decode graphs. */
+int kcpp_model_set_qkv_bias(kcpp_model *m, int il, const float *bq, const float *bk, const float *bv);
 /* koboldcpp's automatic RoPE base for a context beyond the trained one (CalcGradientAIRopeFreqBase,
  * gpttype_adapter.cpp:1598-1640); solar = the reference's ARCH_SOLAR rule (model_adapter.cpp:309) */
 float kcpp_gradient_ai_rope_base(float original_rope_base, int n_ctx_train, int n_ctx_desired, int solar);

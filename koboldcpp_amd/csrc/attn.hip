@@ -395,19 +395,22 @@ static void fa4_dispatch(const uint16_t *q16, const uint16_t *kc, const uint16_t
     float2 *pml = (float2 *)(po + (int64_t)H * NS * 128);
     unsigned long long *st = (unsigned long long *)g_fa_stamps;
     static const bool nt = [] { const char *e = getenv("KCPP_FA_NT"); return !e || atoi(e) != 0; }();
-    if (v5 && n_rows > 0) {
+    // GQA ratios 3, 5, 6, 7 (the Qwen2.5 sizes) always take k_fa_dec5: the legacy A/B kernel is not built for them
+    constexpr bool ONLY5 = G == 3 || G == 5 || G == 6 || G == 7;
+    if (ONLY5 || (v5 && n_rows > 0)) {
         if (nt)
             hipLaunchKernelGGL((k_fa_dec5<G, true>), dim3(NS, HKV), dim3(256), 0, s, q16, kc, vc, po, pml, H, n_past,
                                n_past_dev, NS, scale, kv_ld, kv_hs, n_rows);
         else
             hipLaunchKernelGGL((k_fa_dec5<G, false>), dim3(NS, HKV), dim3(256), 0, s, q16, kc, vc, po, pml, H, n_past,
                                n_past_dev, NS, scale, kv_ld, kv_hs, n_rows);
-    } else if (nt) {
-        hipLaunchKernelGGL((k_fa_dec4<G, true>), dim3(NS, HKV), dim3(256), 0, s, q16, kc, vc, po, pml, H, n_past,
-                           n_past_dev, NS, scale, kv_ld, kv_hs, st);
-    } else {
-        hipLaunchKernelGGL((k_fa_dec4<G, false>), dim3(NS, HKV), dim3(256), 0, s, q16, kc, vc, po, pml, H, n_past,
-                           n_past_dev, NS, scale, kv_ld, kv_hs, st);
+    } else if constexpr (!ONLY5) {
+        if (nt)
+            hipLaunchKernelGGL((k_fa_dec4<G, true>), dim3(NS, HKV), dim3(256), 0, s, q16, kc, vc, po, pml, H, n_past,
+                               n_past_dev, NS, scale, kv_ld, kv_hs, st);
+        else
+            hipLaunchKernelGGL((k_fa_dec4<G, false>), dim3(NS, HKV), dim3(256), 0, s, q16, kc, vc, po, pml, H, n_past,
+                               n_past_dev, NS, scale, kv_ld, kv_hs, st);
     }
     if (qout && qkind == 2)
         hipLaunchKernelGGL((k_fa_comb4<2, NS>), dim3(H / 2), dim3(256), 0, s, po, pml, out, (uint8_t *)qout, H, st,
@@ -453,7 +456,11 @@ static int fa_short_launch(const uint16_t *q16, const uint16_t *kc, const uint16
     switch (G) {
     case 1: KCPP_FS(1); break;
     case 2: KCPP_FS(2); break;
+    case 3: KCPP_FS(3); break;
     case 4: KCPP_FS(4); break;
+    case 5: KCPP_FS(5); break;
+    case 6: KCPP_FS(6); break;
+    case 7: KCPP_FS(7); break;
     case 8: KCPP_FS(8); break;
     default: return -3;
     }
@@ -468,13 +475,17 @@ static int fa4_launch(const uint16_t *q16, const uint16_t *kc, const uint16_t *v
     const int G = H / HKV;
     const int NS = fa4_splits(HKV);
     if (!qout && !out) return -1;
+    if (n_rows < 1 && (G == 3 || G == 5 || G == 6 || G == 7)) return -1;      // k_fa_dec5 only: it needs the views' row count
     int rc = -1;
+#define KCPP_FA4(G_) case G_: rc = fa4_dispatch_ns<G_>(NS, q16, kc, vc, kv_ld, kv_hs, out, qout, ws, H, HKV, n_past, n_past_dev, scale, s, qkind, n_rows, v5); break;
     switch (G) {
+    KCPP_FA4(3) KCPP_FA4(5) KCPP_FA4(6) KCPP_FA4(7)
+#undef KCPP_FA4
     case 1: rc = fa4_dispatch_ns<1>(NS, q16, kc, vc, kv_ld, kv_hs, out, qout, ws, H, HKV, n_past, n_past_dev, scale, s, qkind, n_rows, v5); break;
     case 2: rc = fa4_dispatch_ns<2>(NS, q16, kc, vc, kv_ld, kv_hs, out, qout, ws, H, HKV, n_past, n_past_dev, scale, s, qkind, n_rows, v5); break;
     case 4: rc = fa4_dispatch_ns<4>(NS, q16, kc, vc, kv_ld, kv_hs, out, qout, ws, H, HKV, n_past, n_past_dev, scale, s, qkind, n_rows, v5); break;
     case 8: rc = fa4_dispatch_ns<8>(NS, q16, kc, vc, kv_ld, kv_hs, out, qout, ws, H, HKV, n_past, n_past_dev, scale, s, qkind, n_rows, v5); break;
-    default: return -1;
+    default: return -3;          // a ratio no kernel is built for (as the chunk kernel's dispatch answers)
     }
     if (rc) return rc;
     KCPP_CHECK(hipGetLastError());
@@ -733,7 +744,7 @@ int kcpp_flash_attn_dec_ta(const uint16_t *q16, const uint16_t *kc, const uint16
                            void *stream) {
     if (D != 128 || H % HKV || H % 2 || !qta) return -3;
     const int G = H / HKV;
-    if (!(G == 2 || G == 4 || G == 8)) return -3;
+    if (G < 2 || G > FA_MAXG) return -3;
     return fa4_launch(q16, kc, vc, (int64_t)HKV * 128, 128, out, qta, ws, H, HKV, n_past, n_past_dev, scale,
                       (hipStream_t)stream, 2, n_past_dev ? n_kv_max : n_past + 1, fa_dec5_default());
 }
@@ -764,7 +775,7 @@ int kcpp_flash_attn(const uint16_t *q16, const uint16_t *kc, const uint16_t *vc,
         return fa_short_launch(q16, kc, vc, (int64_t)HKV * 128, 128, out, H, HKV, n_past, n_past_dev, scale, s,
                                n_past_dev ? n_kv_max : n_past + 1);
     }
-    if (use_decode && T == 1 && force_path != 6 && (G0 == 1 || G0 == 2 || G0 == 4 || G0 == 8) && (qout == nullptr || G0 >= 2))
+    if (use_decode && T == 1 && force_path != 6 && (qout == nullptr || G0 >= 2))
         return fa4_launch(q16, kc, vc, (int64_t)HKV * 128, 128, out, qout, ws, H, HKV, n_past, n_past_dev, scale, s, 1,
                           n_past_dev ? n_kv_max : n_past + 1, fa_dec5_default());
     if (use_decode) {
@@ -783,7 +794,11 @@ int kcpp_flash_attn(const uint16_t *q16, const uint16_t *kc, const uint16_t *vc,
         switch (G0) {
             KCPP_FA_CASE(1)
             KCPP_FA_CASE(2)
+            KCPP_FA_CASE(3)
             KCPP_FA_CASE(4)
+            KCPP_FA_CASE(5)
+            KCPP_FA_CASE(6)
+            KCPP_FA_CASE(7)
             KCPP_FA_CASE(8)
         default: return -3;
         }
@@ -825,7 +840,7 @@ int kcpp_fa_decode_ex(const uint16_t *q16, const uint16_t *kc, const uint16_t *v
                       int n_kv_max, float scale, int variant, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     const int G = H / HKV;
-    if (H % HKV || !(G == 1 || G == 2 || G == 4 || G == 8) || (H % 2) || HKV > 64) return -1;
+    if (H % HKV || G < 1 || G > FA_MAXG || (H % 2) || HKV > 64) return -1;
     if (qout && G < 2) return -1;
     const int nkv = n_past_dev ? n_kv_max : n_past + 1;
     if (variant == 3 || variant == 5)
@@ -871,7 +886,7 @@ int kcpp_fa_decode_ex(const uint16_t *q16, const uint16_t *kc, const uint16_t *v
         hipLaunchKernelGGL((k_fa_decode<128, GG>), grid, dim3(256), 0, s, q16, kc, vc, po, pml, 1, H, HKV, n_past, \
                            n_past_dev, nch, scale, nullptr, -1, kv_ld, kv_hs);                                   \
         break;
-    switch (G) { KCPP_FA_CASE(1) KCPP_FA_CASE(2) KCPP_FA_CASE(4) KCPP_FA_CASE(8) }
+    switch (G) { KCPP_FA_CASE(1) KCPP_FA_CASE(2) KCPP_FA_CASE(3) KCPP_FA_CASE(4) KCPP_FA_CASE(5) KCPP_FA_CASE(6) KCPP_FA_CASE(7) KCPP_FA_CASE(8) }
 #undef KCPP_FA_CASE
     KCPP_CHECK(hipGetLastError());
     if (qout) hipLaunchKernelGGL(k_fa_combine<true>, dim3(H / 2, 1), dim3(1024), 0, s, po, pml, out, (uint8_t *)qout, 1, H, 128, n_past, n_past_dev, nch, 0);
@@ -960,7 +975,11 @@ int kcpp_flash_attn_ext(const float *q, int64_t q_nb1, int64_t q_nb2, const uint
         switch (H / HKV) {
             KCPP_FA_CASE(1)
             KCPP_FA_CASE(2)
+            KCPP_FA_CASE(3)
             KCPP_FA_CASE(4)
+            KCPP_FA_CASE(5)
+            KCPP_FA_CASE(6)
+            KCPP_FA_CASE(7)
             KCPP_FA_CASE(8)
         default: return -3;
         }

@@ -107,19 +107,36 @@ __global__ void k_kv_store_q(const float *__restrict__ qkv, int64_t ld, int64_t 
 
 // RoPE of q and k in place in the f32 q|k|v staging rows (same rotation and table as ops.hip k_rope_kv, whose
 // f16 rounding the quantized cache must not see: the reference quantizes the f32 rope output)
+// EX: NeoX pairs (ip, ip + D/2) and the q / k / v biases added first (ops.hip k_rope_kv<true>'s arithmetic, so both
+// kernels' f32 results agree bit for bit); the v rows get their bias in place too (kcpp_kv_store_q reads them here)
+template <bool EX>
 __global__ void k_rope_qk_inplace(float *__restrict__ qkv, int64_t ld, int H, int HKV, int D, int n_past,
-                                  const int32_t *__restrict__ pos_dev, const float2 *__restrict__ rope_tab) {
+                                  const int32_t *__restrict__ pos_dev, const float2 *__restrict__ rope_tab, int neox,
+                                  const float *__restrict__ bq, const float *__restrict__ bk, const float *__restrict__ bv) {
     const int t = blockIdx.x;
     const int p = (pos_dev ? pos_dev[0] : n_past) + t;
     const int half = D / 2;
     float *row = qkv + (int64_t)t * ld;
-    for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < (H + HKV) * half; i += gridDim.y * blockDim.x) {
+    const int npairs = (H + HKV) * half;
+    const int nitems = EX && bv ? npairs + HKV * D : npairs;
+    for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < nitems; i += gridDim.y * blockDim.x) {
+        if (EX && i >= npairs) {
+            float *v = row + (int64_t)(H + HKV) * D + (i - npairs);
+            *v = __fadd_rn(*v, bv[i - npairs]);
+            continue;
+        }
         const int hh = i / half, ip = i % half;           // heads 0..H-1 are q, H..H+HKV-1 are k (contiguous)
         const float2 cs = rope_tab[(int64_t)p * half + ip];
-        float *src = row + (int64_t)hh * D + 2 * ip;
-        const float x0 = src[0], x1 = src[1];
-        src[0] = __fsub_rn(__fmul_rn(x0, cs.x), __fmul_rn(x1, cs.y));
-        src[1] = __fadd_rn(__fmul_rn(x0, cs.y), __fmul_rn(x1, cs.x));
+        const int e0 = EX && neox ? ip : 2 * ip, e1 = EX && neox ? ip + half : 2 * ip + 1;
+        float *src = row + (int64_t)hh * D;
+        float x0 = src[e0], x1 = src[e1];
+        if constexpr (EX) {
+            const float *b = hh < H ? bq : bk;
+            const int hb = hh < H ? hh : hh - H;
+            if (b) { x0 = __fadd_rn(x0, b[hb * D + e0]); x1 = __fadd_rn(x1, b[hb * D + e1]); }
+        }
+        src[e0] = __fsub_rn(__fmul_rn(x0, cs.x), __fmul_rn(x1, cs.y));
+        src[e1] = __fadd_rn(__fmul_rn(x0, cs.y), __fmul_rn(x1, cs.x));
     }
 }
 
@@ -312,13 +329,25 @@ int64_t kcpp_kv_cache_bytes(int type, int64_t n_ctx, int64_t ekv) {
     return -1;
 }
 
-int kcpp_rope_qk_inplace(float *qkv, int64_t ld, int T, int H, int HKV, int D, int n_past, const int32_t *pos_dev,
-                         const void *rope_tab, void *stream) {
-    const int items = (H + HKV) * D / 2;
-    hipLaunchKernelGGL(k_rope_qk_inplace, dim3((unsigned)T, (unsigned)((items + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, qkv, ld, H, HKV, D, n_past, pos_dev, (const float2 *)rope_tab);
+int kcpp_rope_qk_inplace_ex(float *qkv, int64_t ld, int T, int H, int HKV, int D, int n_past, const int32_t *pos_dev,
+                            const void *rope_tab, int mode, const float *bq, const float *bk, const float *bv, void *stream) {
+    if ((mode != 0 && mode != 2) || D < 2 || D % 2) return -1;
+    const bool ex = mode == 2 || bq || bk || bv;
+    const int items = (H + HKV) * D / 2 + (bv ? HKV * D : 0);
+    const dim3 grid((unsigned)T, (unsigned)((items + 255) / 256));
+    if (ex)
+        hipLaunchKernelGGL(k_rope_qk_inplace<true>, grid, dim3(256), 0, (hipStream_t)stream, qkv, ld, H, HKV, D, n_past, pos_dev,
+                           (const float2 *)rope_tab, mode == 2, bq, bk, bv);
+    else
+        hipLaunchKernelGGL(k_rope_qk_inplace<false>, grid, dim3(256), 0, (hipStream_t)stream, qkv, ld, H, HKV, D, n_past,
+                           pos_dev, (const float2 *)rope_tab, 0, (const float *)nullptr, (const float *)nullptr,
+                           (const float *)nullptr);
     KCPP_CHECK(hipGetLastError());
     return 0;
+}
+int kcpp_rope_qk_inplace(float *qkv, int64_t ld, int T, int H, int HKV, int D, int n_past, const int32_t *pos_dev,
+                         const void *rope_tab, void *stream) {
+    return kcpp_rope_qk_inplace_ex(qkv, ld, T, H, HKV, D, n_past, pos_dev, rope_tab, 0, nullptr, nullptr, nullptr, stream);
 }
 
 int kcpp_kv_store_q(int tk, int tv, const float *qkv, int64_t ld, int64_t koff, int64_t voff, int T, int64_t ekv,

@@ -686,34 +686,38 @@ bool load_model(const load_model_inputs inputs) {
     }
     gguf::File &f = e->file;
     const std::string arch = f.get_s("general.architecture", "");
-    if (arch != "llama") { fprintf(stderr, "[kcpp] load_model: architecture '%s' not supported\n", arch.c_str()); return false; }
+    // llama, or qwen2 (the Llama graph with q / k / v biases and NeoX rope pairs: build_qwen2, src/llama.cpp:12136-12246);
+    // the hyper-parameters live under the architecture's own prefix
+    const bool qwen2 = arch == "qwen2";
+    const std::string pfx = arch + ".";
+    if (arch != "llama" && !qwen2) { fprintf(stderr, "[kcpp] load_model: architecture '%s' not supported\n", arch.c_str()); return false; }
     if (!e->tok.init(f, err)) { fprintf(stderr, "[kcpp] load_model: %s\n", err.c_str()); return false; }
     const gguf::Tensor *emb = f.tensor("token_embd.weight");
     if (!emb) { fprintf(stderr, "[kcpp] load_model: no token_embd.weight\n"); return false; }
     kcpp_hparams &hp = e->hp;
-    hp.n_embd = (int)f.get_i("llama.embedding_length", emb->ne[0]);
+    hp.n_embd = (int)f.get_i(pfx + "embedding_length", emb->ne[0]);
     hp.n_vocab = (int)emb->ne[1];
-    hp.n_layer = (int)f.get_i("llama.block_count", 0);
-    hp.n_ff = (int)f.get_i("llama.feed_forward_length", 0);
-    hp.n_head = (int)f.get_i("llama.attention.head_count", 0);
-    hp.n_head_kv = (int)f.get_i("llama.attention.head_count_kv", hp.n_head);
-    hp.eps = (float)f.get_f("llama.attention.layer_norm_rms_epsilon", 1e-5);
+    hp.n_layer = (int)f.get_i(pfx + "block_count", 0);
+    hp.n_ff = (int)f.get_i(pfx + "feed_forward_length", 0);
+    hp.n_head = (int)f.get_i(pfx + "attention.head_count", 0);
+    hp.n_head_kv = (int)f.get_i(pfx + "attention.head_count_kv", hp.n_head);
+    hp.eps = (float)f.get_f(pfx + "attention.layer_norm_rms_epsilon", 1e-5);
     // RoPE (gpttype_adapter.cpp:1677-1700, 1926-1950): a user --ropeconfig (rope_freq_scale > 0) wins; a model that
     // sets its own RoPE (freq_base not 10000 / 500000, a linear scale, or YaRN) keeps its values; otherwise the base
     // is auto-scaled for the requested context by the GradientAI rule (CalcGradientAIRopeFreqBase)
-    const float base_train = (float)f.get_f("llama.rope.freq_base", 10000.0);
-    float ropescale = (float)f.get_f("llama.rope.scaling.factor", 0.0);
-    if (ropescale == 0.0f) ropescale = (float)f.get_f("llama.rope.scale_linear", 0.0);
+    const float base_train = (float)f.get_f(pfx + "rope.freq_base", 10000.0);
+    float ropescale = (float)f.get_f(pfx + "rope.scaling.factor", 0.0);
+    if (ropescale == 0.0f) ropescale = (float)f.get_f(pfx + "rope.scale_linear", 0.0);
     const float scale_train = ropescale == 0.0f ? 1.0f : 1.0f / ropescale;
     // YaRN is refused only where the model's own RoPE values would be used: a user --ropeconfig replaces them and the
     // reference then never reads the model's YaRN settings (gpttype_adapter.cpp:1681-1687, 1926-1930)
-    if (f.get_s("llama.rope.scaling.type", "") == "yarn" && !(inputs.rope_freq_scale > 0.0f)) {
+    if (f.get_s(pfx + "rope.scaling.type", "") == "yarn" && !(inputs.rope_freq_scale > 0.0f)) {
         fprintf(stderr, "[kcpp] load_model: YaRN rope scaling is not supported (pass --ropeconfig to override)\n");
         return false;
     }
-    const int n_ctx_train = (int)f.get_i("llama.context_length", 2048);     // FileFormatExtraMeta default
+    const int n_ctx_train = (int)f.get_i(pfx + "context_length", 2048);     // FileFormatExtraMeta default
     // ARCH_SOLAR (model_adapter.cpp:309): llama, freq_base 10000, 435 or 611 tensors
-    const bool solar = base_train == 10000.0f && (f.tensors.size() == 435 || f.tensors.size() == 611);
+    const bool solar = !qwen2 && base_train == 10000.0f && (f.tensors.size() == 435 || f.tensors.size() == 611);
     if (inputs.rope_freq_scale > 0.0f) {
         hp.rope_base = inputs.rope_freq_base;
         hp.rope_freq_scale = inputs.rope_freq_scale;
@@ -729,9 +733,20 @@ bool load_model(const load_model_inputs inputs) {
         fprintf(stderr, "[kcpp] load_model: need head_dim 128 or 64 (got n_embd %d / n_head %d)\n", hp.n_embd, hp.n_head);
         return false;
     }
+    if (qwen2) {
+        // shapes no kernel takes are refused here, never at a launch: an even head count, whole GQA groups of at most 8
+        // query heads (the decode attention's FA_MAXG), no experts (qwen2moe is another architecture)
+        const int hkv = hp.n_head_kv;
+        if (hp.n_head % 2 || hkv < 1 || hp.n_head % hkv || hp.n_head / hkv > 8 || hp.n_embd % hp.n_head) {
+            fprintf(stderr, "[kcpp] load_model: qwen2: unsupported head layout %d / %d (need an even head count and a GQA "
+                            "ratio of at most 8)\n", hp.n_head, hkv);
+            return false;
+        }
+        if (f.get_i(pfx + "expert_count", 0) > 0) { fprintf(stderr, "[kcpp] load_model: qwen2 with experts is not supported\n"); return false; }
+    }
     // mixture of experts (llm_load_hparams / llm_load_tensors, src/llama.cpp:5444-5445, 7176-7215)
-    hp.n_expert = (int)f.get_i("llama.expert_count", 0);
-    hp.n_expert_used = (int)f.get_i("llama.expert_used_count", 0);
+    hp.n_expert = (int)f.get_i(pfx + "expert_count", 0);
+    hp.n_expert_used = (int)f.get_i(pfx + "expert_used_count", 0);
     if (hp.n_expert > 0 && (hp.n_expert_used < 1 || hp.n_expert_used > hp.n_expert || hp.n_expert > 64)) {
         fprintf(stderr, "[kcpp] load_model: unsupported expert_count %d / expert_used_count %d\n", hp.n_expert,
                 hp.n_expert_used);
@@ -791,6 +806,31 @@ bool load_model(const load_model_inputs inputs) {
         }
         e->types[k] = ts[k].type;
     }
+    // qwen2: blk.N.attn_{q,k,v}.bias, all three required, F32 with n_embd / n_embd_gqa / n_embd_gqa values
+    // (llm_load_tensors, src/llama.cpp:7739-7777); every matrix row must be whole blocks of its type
+    std::vector<const float *> qkv_bias;
+    if (qwen2) {
+        const int64_t ekv = (int64_t)hp.n_head_kv * (hp.n_embd / hp.n_head);
+        for (size_t k = 0; k < ts.size(); ++k)
+            if (ts[k].t->ne[0] % ks_block_elems(ts[k].type)) {
+                fprintf(stderr, "[kcpp] load_model: %s: row length %lld is not a multiple of the type's block\n",
+                        ts[k].t->name.c_str(), (long long)ts[k].t->ne[0]);
+                return false;
+            }
+        static const char *bn[3] = {"attn_q.bias", "attn_k.bias", "attn_v.bias"};
+        for (int il = 0; il < hp.n_layer; ++il)
+            for (int j = 0; j < 3; ++j) {
+                const std::string name = "blk." + std::to_string(il) + "." + bn[j];
+                const gguf::Tensor *bt = f.tensor(name);
+                const int64_t want = j == 0 ? hp.n_embd : ekv;
+                if (!bt || bt->type != KT_F32 || bt->ne[0] != want || bt->ne[1] * bt->ne[2] * bt->ne[3] != 1) {
+                    fprintf(stderr, "[kcpp] load_model: %s: %s (expected %lld F32 values)\n", name.c_str(),
+                            bt ? "wrong type or length" : "missing tensor", (long long)want);
+                    return false;
+                }
+                qkv_bias.push_back((const float *)bt->data);
+            }
+    }
     // n_gpu_layers (src/llama.cpp:6977-7036: layers [0, n_layer - n_gpu_layers) stay on the CPU backend): this backend
     // has no CPU compute path, so a partial offload is refused instead of silently becoming a full one; negative
     // (koboldcpp's auto) and >= n_layer offload everything (the output head, which the reference keeps on the CPU
@@ -840,6 +880,17 @@ bool load_model(const load_model_inputs inputs) {
                 fprintf(stderr, "[kcpp] load_model: rope_freqs: %s\n", kcpp_last_error());
                 return false;
             }
+    if (qwen2)       // NeoX pairs (llama_rope_type, src/llama.cpp:19731) and the biases, on every stage for its layers
+        for (kcpp_model *m : e->stages) {
+            if (kcpp_model_set_rope_mode(m, 2)) { fprintf(stderr, "[kcpp] load_model: rope mode: %s\n", kcpp_last_error()); return false; }
+            for (int il = 0; il < hp.n_layer; ++il) {
+                if (!kcpp_model_owns_layer(m, il)) continue;
+                if (kcpp_model_set_qkv_bias(m, il, qkv_bias[3 * il], qkv_bias[3 * il + 1], qkv_bias[3 * il + 2])) {
+                    fprintf(stderr, "[kcpp] load_model: blk.%d q/k/v bias: %s\n", il, kcpp_last_error());
+                    return false;
+                }
+            }
+        }
     for (size_t k = 0; k < ts.size(); ++k) {
         for (kcpp_model *m : e->stages)
             if (kcpp_model_set_tensor(m, (int)k, ts[k].data, ts[k].bytes)) {

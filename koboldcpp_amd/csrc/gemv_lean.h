@@ -181,6 +181,45 @@ struct ActCopyCol {
     }
 };
 
+// MODE 2 with DecArgs.bias / rope_neox (EX instances, R = 2): the rows of group g2 = row0 / 2 of a segment.  NeoX pairs
+// in the q and k roles: g2 -> (h D + j, h D + j + D/2), h = g2 / (D/2), j = g2 % (D/2) -- the rotation pair of ggml's
+// NeoX mode, so one lane still holds both halves of a rotation; otherwise (v, or NORM pairs) rows (row0, row0 + 1).
+__device__ __forceinline__ void ex_group_rows(const DecArgs &a, int role, int row0, int &base, int &stride) {
+    base = row0;
+    stride = 1;
+    if (a.rope_neox && role != 2) {
+        const int hd = a.D / 2, g2 = row0 / 2;
+        base = (g2 / hd) * a.D + g2 % hd;
+        stride = hd;
+    }
+}
+// the EX epilogue of one group: x = product + bias[row] (f32 ggml_add in front of the rope), the rotation with table
+// entry j (the same __fmul_rn / __fsub_rn / __fadd_rn as the NORM path), f16 stores at the rows' own places (NeoX: two
+// 2-byte stores D/2 apart -- q16 and the K cache hold the true NeoX layout)
+__device__ __forceinline__ void store_group_ex(const DecArgs &a, int seg, int row0, const float (&slot)[2]) {
+    const int role = seg == 0 ? a.role[0] : (seg == 1 ? a.role[1] : a.role[2]);
+    const float *bias = seg == 0 ? a.bias[0] : (seg == 1 ? a.bias[1] : a.bias[2]);
+    const int p = a.pos[0];
+    int base, stride;
+    ex_group_rows(a, role, row0, base, stride);
+    const int ra = base, rb = base + stride;
+    const float x0 = bias ? __fadd_rn(slot[0], bias[ra]) : slot[0];
+    const float x1 = bias ? __fadd_rn(slot[1], bias[rb]) : slot[1];
+    if (role == 2) {
+        a.vc[(int64_t)p * a.ekv + ra] = f2h(x0);
+        a.vc[(int64_t)p * a.ekv + rb] = f2h(x1);
+        return;
+    }
+    const int hd = a.D / 2;
+    const int j = a.rope_neox ? ra % a.D : (ra % a.D) / 2;       // NeoX: ra % D = j < D/2
+    const float2 cs = a.rope_tab[(int64_t)p * hd + j];
+    const float o0 = __fsub_rn(__fmul_rn(x0, cs.x), __fmul_rn(x1, cs.y));
+    const float o1 = __fadd_rn(__fmul_rn(x0, cs.y), __fmul_rn(x1, cs.x));
+    uint16_t *dst = role == 0 ? a.q16 : a.kc + (int64_t)p * a.ekv;
+    dst[ra] = f2h(o0);
+    dst[rb] = f2h(o1);
+}
+
 // store R parked results of group slot_g (rows row0.. of segment seg)
 template <int R, int MODE, bool AUX = false>
 __device__ __forceinline__ void store_group(const DecArgs &a, int seg, int row0, const float (&slot)[R],

@@ -226,6 +226,7 @@ extern "C" int kcpp_gemv_q4k(const void *args, int mode, int pro, void *stream) 
     const DecArgs &a = *(const DecArgs *)args;
     hipStream_t s = (hipStream_t)stream;
     if (a.nseg < 1 || a.nseg > 3) return -3;
+    if (mode == 2 && dec_args_ex(a)) return -3;          // q|k|v bias / NeoX pairs: the RS kernels only
     // gate|up: R = 2 with prefetch at 256 workgroups (17.5 us vs 21.1 us for gemv_dec_impl.h)
     if (a.K == 4096) {
         if (mode == 1 && pro == 1) return launch_q4k<1, 2, 1, 1, 1, 1>(a, s);

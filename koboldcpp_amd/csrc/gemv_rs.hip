@@ -61,10 +61,19 @@ using namespace rs;
 // MODE 3 (MoE, both top-2 slots' down projections in one launch, NWV = 8, PRO 2): waves 0-3 stream expert eid's rows
 // against slot 0's h (x), waves 4-7 the same rows of expert eid1 against slot 1's h (x + K); the halves meet in LDS and
 // the row is ((w0 o0) + (w1 o1)) + res -- the two chained MODE 0 launches' result bit for bit
-template <int TYPE, int NI, int R, int MODE, int PRO, int MC, int PF, int NWV = 4, bool XL = false, bool ROUTE = false>
-__global__ void __launch_bounds__(64 * NWV) k_gemv_rs(const DecArgs a) {
+// EX (MODE 2, R = 2; the Qwen2 class): DecArgs.bias added to the products and, with rope_neox, the q / k groups are the
+// NeoX rotation pairs (rows j and j + D/2 of a head: lean::ex_group_rows) -- separate instances, so the Llama launches
+// (no bias, NORM pairs) run the instructions they ran before
+template <int TYPE, int NI, int R, int MODE, int PRO, int MC, int PF, int NWV = 4, bool XL = false, bool ROUTE = false,
+          bool EX = false>
+__global__ void __launch_bounds__(64 * NWV) k_gemv_rs(const int kb_nblk, const DecArgs a) {
+    static_assert(!EX || (MODE == 2 && R == 2), "EX: the q|k|v launch");
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const int KB_BID = (int)blockIdx.x, KB_NBLK = (int)gridDim.x;
+    // the workgroup count as the first explicit argument, not gridDim.x.  Measured: growing DecArgs by bias[] /
+    // rope_neox alone took the bench decode from 617 to 607 tok/s, and reading the count here instead brought it back
+    // (profiles/qwen2_kernarg_ab.jsonl).  Supposed, not shown: the implicit arguments lie behind DecArgs, and a load
+    // from them past byte 320 of the argument block is what costs the ~0.14 us per launch
+    const int KB_BID = (int)blockIdx.x, KB_NBLK = kb_nblk;
     constexpr bool AUX = false;
     float *const aux0 = nullptr, *const aux1 = nullptr, *const aux2 = nullptr;
     uint16_t *const auxh = nullptr;
@@ -75,10 +84,10 @@ __global__ void __launch_bounds__(64 * NWV) k_gemv_rs(const DecArgs a) {
 // the ggml plugin's fused nodes (AuxOut): the same body storing the intermediate nodes' tensors too -- MODE 0 the
 // product before the residual, MODE 1 gate, silu(gate) and up beside the GLU product
 template <int TYPE, int NI, int R, int MODE, int PRO, int MC, int PF, int NWV>
-__global__ void __launch_bounds__(64 * NWV) k_gemv_rs_aux(const DecArgs a, const AuxOut o) {
+__global__ void __launch_bounds__(64 * NWV) k_gemv_rs_aux(const int kb_nblk, const DecArgs a, const AuxOut o) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const int KB_BID = (int)blockIdx.x, KB_NBLK = (int)gridDim.x;
-    constexpr bool XL = false, ROUTE = false, AUX = true;
+    const int KB_BID = (int)blockIdx.x, KB_NBLK = kb_nblk;
+    constexpr bool XL = false, ROUTE = false, AUX = true, EX = false;
     float *const aux0 = o.p0, *const aux1 = o.p1, *const aux2 = o.p2;
     uint16_t *const auxh = o.h0;
     const RopeP rp = o.rope;
@@ -91,7 +100,7 @@ namespace {
 thread_local const AuxOut *g_rs_aux = nullptr;
 
 template <int TYPE, int NI, int R, int MODE, int PRO, int MC, int PF, int NWV = 4, bool XL = false, bool ROUTE = false,
-          bool AUX = false>
+          bool AUX = false, bool EX = false>
 int launch_rs(const DecArgs &a, int max_blocks, hipStream_t s) {
     int64_t ntot = 0;
     for (int i = 0; i < a.nseg; ++i) {
@@ -107,10 +116,10 @@ int launch_rs(const DecArgs &a, int max_blocks, hipStream_t s) {
     if constexpr (AUX) {
         static_assert(!XL && !ROUTE, "AUX instances: plain single-token launches");
         hipLaunchKernelGGL((k_gemv_rs_aux<TYPE, NI, R, MODE, PRO, MC, PF, NWV>), dim3((unsigned)nblk), dim3(64 * NWV),
-                           (size_t)lbytes + 16, s, a, *g_rs_aux);
+                           (size_t)lbytes + 16, s, (int)nblk, a, *g_rs_aux);
     } else {
-        hipLaunchKernelGGL((k_gemv_rs<TYPE, NI, R, MODE, PRO, MC, PF, NWV, XL, ROUTE>), dim3((unsigned)nblk), dim3(64 * NWV),
-                           (size_t)lbytes + 16, s, a);
+        hipLaunchKernelGGL((k_gemv_rs<TYPE, NI, R, MODE, PRO, MC, PF, NWV, XL, ROUTE, EX>), dim3((unsigned)nblk), dim3(64 * NWV),
+                           (size_t)lbytes + 16, s, (int)nblk, a);
     }
     KCPP_CHECK(hipGetLastError());
     return 0;
@@ -140,6 +149,11 @@ int pick_rs(const DecArgs &a, int mode, int pro, hipStream_t s) {
     // the ggml plugin's fused nodes (aux: the intermediate nodes' tensors stored too), separate instances so the
     // runtime's launches carry none of it: MUL_MAT -> ADD as the plain single-token launch below (quantize prologue,
     // 8 waves), the SiLU GLU as KCPP_RS_P(2)'s mode 1
+    // q|k|v with bias / NeoX pairs (kcpp_gemv_rs checked the shapes): the mode-2 launch's EX instance, norm prologue
+    if (mode == 2 && dec_args_ex(a)) {
+        if (g_rs_aux || pro != 1) return -3;
+        return launch_rs<TYPE, NI, 2, 2, 1, MC, 0, 4, false, false, false, true>(a, B, s);
+    }
     if (g_rs_aux) {
         // with a ROPE behind the product: two rows per group (a rope pair in one lane), as the runtime's q|k|v launch
         if (g_rs_aux->rope.out) {
@@ -189,7 +203,7 @@ int pick_rs(const DecArgs &a, int mode, int pro, hipStream_t s) {
 // the shape rounds up to.
 template <int TYPE, int NI>
 int pick_rs_xl(const DecArgs &a, int mode, int pro, hipStream_t s) {
-    if (g_rs_aux) return -3;
+    if (g_rs_aux || (mode == 2 && dec_args_ex(a))) return -3;
     constexpr int MC = TYPE == KT_Q6_K_RS ? NI : NI / 2;        // ceil(K / 4096) at the ceiling
     if (mode == 0) {
         if (pro == 2) return launch_rs<TYPE, NI, 1, 0, 2, MC, 0, 8, true>(a, 256, s);
@@ -224,8 +238,8 @@ int dispatch_rs_xl(const DecArgs &a, int ni, int mode, int pro, hipStream_t s) {
 // kernel of its own: prologue, one group per wave, epilogue), segments 0 / 1 (q, k) run the Q4_K_RS path and
 // segment 2 (v) the Q6_K_RS path of one grid over the same LDS activation (rms_norm -> Q8_K prologue, both types'
 // vec_dot_type); groups are wave-uniform in type.  Mode 2 epilogue (RoPE + f16 q / K / V stores), R = 2.
-template <int NIA, int NIB, int MC>
-__global__ void __launch_bounds__(256) k_gemv_rs_qkv(const DecArgs a) {
+template <int NIA, int NIB, int MC, bool EX = false>
+__global__ void __launch_bounds__(256) k_gemv_rs_qkv(const int kb_nblk, const DecArgs a) {   // kb_nblk: see k_gemv_rs
     using TA = RS<KT_Q4_K_RS>;
     using TB = RS<KT_Q6_K_RS>;
     constexpr int R = 2;
@@ -237,7 +251,7 @@ __global__ void __launch_bounds__(256) k_gemv_rs_qkv(const DecArgs a) {
     const int npA = nsb * TA::PIECES_PER_SB, npB = nsb * TB::PIECES_PER_SB;
     const int N0 = (int)a.N[0], N1 = (int)a.N[1], N2 = (int)a.N[2];
     const int ngA = (N0 + N1) / R, ngroups = ngA + N2 / R;
-    const int nw = (int)gridDim.x * 4;
+    const int nw = kb_nblk * 4;
     const int wid = (int)blockIdx.x * 4 + wave;
     const typename TA::Lane lca = TA::lane_consts(lane);
     const typename TB::Lane lcb = TB::lane_consts(lane);
@@ -257,10 +271,14 @@ __global__ void __launch_bounds__(256) k_gemv_rs_qkv(const DecArgs a) {
         int seg, row0;
         group_rows(g, seg, row0);
         const uint8_t *W = seg == 0 ? a.W[0] : a.W[1];
+        int rbase = row0, rstride = 1;      // EX: NeoX pairs in the q / k roles (lean::ex_group_rows)
+        if constexpr (EX) lean::ex_group_rows(a, seg == 0 ? a.role[0] : a.role[1], row0, rbase, rstride);
 #pragma unroll
-        for (int r = 0; r < R; ++r)
+        for (int r = 0; r < R; ++r) {
+            const int wrow = EX ? rbase + r * rstride : row0 + r;
 #pragma unroll
-            for (int i = 0; i < NIA; ++i) TA::load(W + (int64_t)(row0 + r) * RBA, nsb, min(lane + 64 * i, npA - 1), b.w[i][r]);
+            for (int i = 0; i < NIA; ++i) TA::load(W + (int64_t)wrow * RBA, nsb, min(lane + 64 * i, npA - 1), b.w[i][r]);
+        }
     };
     auto issueB = [&](int g, BufB &b) {
         const int row0 = (g - ngA) * R;
@@ -315,7 +333,8 @@ __global__ void __launch_bounds__(256) k_gemv_rs_qkv(const DecArgs a) {
     if (slot_g < 0) return;
     int seg, row0;
     group_rows(slot_g, seg, row0);
-    lean::store_group<R, 2>(a, seg, row0, slot);
+    if constexpr (EX) lean::store_group_ex(a, seg, row0, slot);
+    else lean::store_group<R, 2>(a, seg, row0, slot);
 }
 
 // q|k|v decode projection with q, k in Q4_K_RS and v in Q6_K_RS (segments 0, 1, 2): one launch.  -3 when not covered.
@@ -323,6 +342,10 @@ extern "C" int kcpp_gemv_rs_qkv_mixed(const void *args, void *stream) {
     const DecArgs &a = *(const DecArgs *)args;
     if (a.nseg != 3 || a.K % 256 || !kcpp_rs_supported(KT_Q4_K_RS, a.K) || !kcpp_rs_supported(KT_Q6_K_RS, a.K)) return -3;
     if (a.N[0] % 2 || a.N[1] % 2 || a.N[2] % 2) return -5;
+    // bias / NeoX pairs (the EX instances): segments 0, 1 = q, k and 2 = v as the runtime passes them; whole heads
+    const bool ex = dec_args_ex(a);
+    if (ex && (a.role[0] != 0 || a.role[1] != 1 || a.role[2] != 2)) return -3;
+    if (ex && a.rope_neox && (a.D < 2 || a.D % 2 || a.N[0] % a.D || a.N[1] % a.D)) return -3;
     const int nsb = (int)(a.K / 256);
     const int nia = (nsb * 8 + 63) / 64, nib = (nsb * 4 + 63) / 64, mc = (int)((a.K + 4095) / 4096);
     const int64_t groups = (a.N[0] + a.N[1] + a.N[2]) / 2;
@@ -330,7 +353,11 @@ extern "C" int kcpp_gemv_rs_qkv_mixed(const void *args, void *stream) {
     nblk = std::max<int64_t>(nblk, (groups + 255) / 256);
     const int64_t abytes = a.K + a.K / 256 * 4 + a.K / 16 * 2;
     hipStream_t s = (hipStream_t)stream;
-#define KCPP_QKVM(A_, B_, M_) hipLaunchKernelGGL((k_gemv_rs_qkv<A_, B_, M_>), dim3((unsigned)nblk), dim3(256), (size_t)abytes + 16, s, a)
+#define KCPP_QKVM(A_, B_, M_)                                                                                          \
+    do {                                                                                                              \
+        if (ex) hipLaunchKernelGGL((k_gemv_rs_qkv<A_, B_, M_, true>), dim3((unsigned)nblk), dim3(256), (size_t)abytes + 16, s, (int)nblk, a); \
+        else hipLaunchKernelGGL((k_gemv_rs_qkv<A_, B_, M_>), dim3((unsigned)nblk), dim3(256), (size_t)abytes + 16, s, (int)nblk, a);         \
+    } while (0)
     if (nia == 2 && nib == 1 && mc == 1) KCPP_QKVM(2, 1, 1);          // n_embd 4096 (Llama-3-8B)
     else if (nia == 4 && nib == 2 && mc == 2) KCPP_QKVM(4, 2, 2);     // n_embd 8192 (Llama-3-70B)
     else if (nia == 1 && nib == 1 && mc == 1) KCPP_QKVM(1, 1, 1);
@@ -352,7 +379,7 @@ template <int TA, int NIA, int MCA, int ITB>
 __global__ void __launch_bounds__(256) k_gemv_qkv_dual(const DecArgs a, const DecArgs b, int nA) {
     if ((int)blockIdx.x < nA) {
         constexpr int TYPE = TA, NI = NIA, R = 2, MODE = 2, PRO = 1, MC = MCA, PF = 0, NWV = 4;
-        constexpr bool XL = false, ROUTE = false, AUX = false;
+        constexpr bool XL = false, ROUTE = false, AUX = false, EX = false;
         float *const aux0 = nullptr, *const aux1 = nullptr, *const aux2 = nullptr;
         uint16_t *const auxh = nullptr;
         const RopeP rp{};
@@ -377,6 +404,7 @@ extern "C" int kcpp_gemv_qkv_dual(const void *qargs, int qtype, const void *kvar
     const DecArgs &b = *(const DecArgs *)kvargs;
     if (qtype != KT_Q4_K_RS && qtype != KT_Q5_K_RS && qtype != KT_Q6_K_RS) return -3;
     if (a.K != b.K || a.K % 256 || a.K > 4096 || !kcpp_rs_supported(qtype, a.K) || a.route_w) return -3;
+    if (dec_args_ex(a) || dec_args_ex(b)) return -3;     // bias / NeoX pairs: not in this grid (the caller falls back)
     int64_t na_rows = 0;
     for (int i = 0; i < a.nseg; ++i) {
         if (a.N[i] % 2) return -5;
@@ -443,6 +471,13 @@ extern "C" int kcpp_gemv_rs(int type, const void *args, int mode, int pro, void 
     if (mode == 3) return pro == 2 && kcpp_rs_supported(type, a.K) ? pick_rs_pair(type, a, s) : -3;
     if (a.nseg < 1 || a.nseg > 3 || !kcpp_rs_supported(type, a.K)) return -3;
     if (mode == 1 && a.nseg != 1 && !(a.nseg == 2 && (a.eid1 || a.route_w))) return -3;   // GLU: one segment, or two MoE slots
+    if (mode == 2 && dec_args_ex(a)) {      // bias / NeoX pairs: dense weights; NeoX groups are pairs inside whole heads
+        if (a.eid || a.route_w) return -3;
+        for (int i = 0; i < a.nseg; ++i) {
+            if (a.role[i] < 0 || a.role[i] > 2) return -3;
+            if (a.rope_neox && a.role[i] != 2 && (a.D < 2 || a.D % 2 || a.N[i] % a.D)) return -3;
+        }
+    }
     const int nsb = (int)(a.K / 256);
     if (type == KT_Q4_K_RS) {
         const int ni = (nsb * 8 + 63) / 64, mc = (int)((a.K + 4095) / 4096);

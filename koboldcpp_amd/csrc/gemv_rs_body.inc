@@ -1,7 +1,7 @@
 // gemv_rs_body.inc -- the body of gemv_rs.hip k_gemv_rs, included by that kernel and by k_gemv_qkv_dual (a grid
 // holding two launches' workgroups).  In scope: the DecArgs `a` (the kernel's own parameter: a copy or a reference
 // would move it to scratch memory), the template names of k_gemv_rs, `lds` (dynamic LDS), KB_BID / KB_NBLK (this
-// workgroup's index and the workgroup count of its launch).
+// workgroup's index and the workgroup count of its launch), EX (MODE 2, R = 2 with DecArgs.bias / rope_neox honoured).
     using T = RS<TYPE>;
     constexpr int RR = MODE == 1 ? 2 * R : R;
     static_assert(MODE != 3 || (NWV == 8 && PRO == 2 && !ROUTE), "MODE 3: 8 waves, quantize prologue");
@@ -50,9 +50,12 @@
             if (hx) eo = eoff1;
         }
         const uint8_t *W = (seg == 0 ? a.W[0] : (seg == 1 ? a.W[1] : a.W[2])) + eo;
+        int rbase = row0, rstride = 1;      // EX: the group's rows (NeoX pairs in the q / k roles, lean::ex_group_rows)
+        if constexpr (EX) lean::ex_group_rows(a, seg == 0 ? a.role[0] : (seg == 1 ? a.role[1] : a.role[2]), row0, rbase, rstride);
 #pragma unroll
         for (int r = 0; r < RR; ++r) {
-            const uint8_t *rp = (MODE == 1 && r >= R ? a.W2 + eo : W) + (int64_t)(row0 + (r % R)) * RB;
+            const int wrow = EX ? rbase + (r % R) * rstride : row0 + (r % R);
+            const uint8_t *rp = (MODE == 1 && r >= R ? a.W2 + eo : W) + (int64_t)wrow * RB;
 #pragma unroll
             for (int i = 0; i < NI; ++i) T::load(rp, nsb, min(lane + 64 * i, npieces - 1), b.w[i][r]);
         }
@@ -253,7 +256,8 @@
             aux2[row0 + r] = sup[r];
         }
     }
-    lean::store_group<R, MODE, AUX>(a, seg, row0, slot, aux0, auxh, rp);
+    if constexpr (EX) lean::store_group_ex(a, seg, row0, slot);
+    else lean::store_group<R, MODE, AUX>(a, seg, row0, slot, aux0, auxh, rp);
 #ifdef KCPP_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     RS_STAMP(4);

@@ -321,6 +321,7 @@ extern "C" int kcpp_gemv_stream(int type, const void *args, int mode, int pro, v
     const DecArgs &a = *(const DecArgs *)args;
     hipStream_t s = (hipStream_t)stream;
     if (type != KT_Q4_K || a.K % 256 || a.nseg < 1 || a.nseg > 3 || a.eid) return -3;
+    if (mode == 2 && dec_args_ex(a)) return -3;          // q|k|v bias / NeoX pairs: the RS kernels only
     // measured (tools/stream_probe.py): only the K = 14336 quantize-prologue shape (ffn_down in the kcpp Q4_K
     // layout) beats the unit-per-lane kernel (20.3 vs 24.6 us); at K = 4096 it loses on VALU work per byte
     if (a.K == 14336 && mode == 0 && pro == 2) return launch_stream<64, 8, 0, 2, 4>(a, s);   // one row per wave

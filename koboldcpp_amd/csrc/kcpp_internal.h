@@ -71,7 +71,14 @@ struct DecArgs {
     int route_ne;
     int32_t *route_ids;
     float *route_wts;
+    // MODE 2 (Qwen2 class): bias[i] (f32 [N[i]], may be null) is added to segment i's product before the rotation /
+    // the V store; rope_neox: the q / k rotation pairs rows (j, j + D/2) of a head (ggml's NeoX mode) instead of
+    // (2j, 2j + 1).  All zero = no bias, NORM pairs.  Only the RS kernels (gemv_rs.hip) take them: every other
+    // mode-2 implementation answers -3 when one is set.
+    const float *bias[3];
+    int rope_neox;
 };
+static inline bool dec_args_ex(const DecArgs &a) { return a.rope_neox || a.bias[0] || a.bias[1] || a.bias[2]; }
 // the ggml plugin's fused nodes (ggml_backend.cpp fuse_*): the intermediate nodes' outputs, written beside Y so that
 // the graph's every tensor holds what the unfused node sequence leaves.  MODE 0: p0 = the product before the residual
 // (the MUL_MAT node under an ADD; null without one), h0 = the product as f16 (a CPY into a contiguous F16 cache view;
@@ -195,6 +202,8 @@ int kcpp_link_wait(const KLink &L, hipStream_t s);
 int kcpp_link_publish(const KLink &L, hipStream_t s);
 // the stage's single-token graph bracketed by the link kernels (runtime.cpp); -3 when graphs are off (row split)
 int kcpp_model_set_link(kcpp_model *m, const KLink *L);
+// whether layer il is one of the stage's own [il0, il1) (the loader hands per-layer data to the owning stage only)
+bool kcpp_model_owns_layer(const kcpp_model *m, int il);
 int kcpp_model_step_linked(kcpp_model *m, int n_past);
 // one query of FLASH_ATTN_EXT in the ggml graph form on the split decode kernel (attn.hip; the b1 backend's decode)
 extern "C" int kcpp_flash_attn_ext_dec(const float *q, int64_t q_nb2, const uint16_t *kc, const uint16_t *vc, int64_t k_ld,

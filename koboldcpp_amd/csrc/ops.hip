@@ -128,10 +128,15 @@ __global__ void __launch_bounds__(1024) k_rms_norm(const float *__restrict__ x, 
 // Outputs: q_out f32 [T][H][D] (roped), q16 f16 copy (FA operand), K/V caches f16 [pos][HKV*D].
 // rope_tab [pos][D/2] (cos, sin) is built on the host exactly as ggml_rope_cache_init
 // (ggml.c:14246) computes it, so the rotation is bit-identical to the CPU op.
+// EX: `neox` pairs elements (ip, ip + D/2) of a head (ggml's NeoX mode, GGML_ROPE_TYPE_NEOX) instead of (2 ip, 2 ip + 1),
+// and bq / bk / bv (f32 [H*D] / [HKV*D] / [HKV*D], may be null) are added to the rows first (the f32 ggml_add of
+// build_qwen2 in front of the rope).  EX = false is the Llama kernel as it was.
+template <bool EX>
 __global__ void k_rope_kv(const float *__restrict__ qkv, int64_t ldqkv, float *__restrict__ q_out,
                           uint16_t *__restrict__ q16, uint16_t *__restrict__ kc, uint16_t *__restrict__ vc,
                           int H, int HKV, int D, int n_past, const int32_t *__restrict__ pos_dev,
-                          const float2 *__restrict__ rope_tab) {
+                          const float2 *__restrict__ rope_tab, int neox, const float *__restrict__ bq,
+                          const float *__restrict__ bk, const float *__restrict__ bv) {
     const int t = blockIdx.x;
     const int p = pos_dev ? pos_dev[t] : n_past + t;
     const int half = D / 2;
@@ -145,21 +150,30 @@ __global__ void k_rope_kv(const float *__restrict__ qkv, int64_t ldqkv, float *_
             const int hh = pi / half, ip = pi % half;
             const float2 cs = rope_tab[(int64_t)p * half + ip];
             const float c = cs.x, s = cs.y;
-            const float *src = isq ? row + (int64_t)hh * D + 2 * ip : row + (int64_t)H * D + (int64_t)hh * D + 2 * ip;
-            const float x0 = src[0], x1 = src[1];
+            const int e0 = EX && neox ? ip : 2 * ip, e1 = EX && neox ? ip + half : 2 * ip + 1;   // elements of the head
+            const float *src = isq ? row + (int64_t)hh * D : row + (int64_t)H * D + (int64_t)hh * D;
+            float x0 = src[e0], x1 = src[e1];
+            if constexpr (EX) {
+                const float *b = isq ? bq : bk;
+                if (b) { x0 = __fadd_rn(x0, b[hh * D + e0]); x1 = __fadd_rn(x1, b[hh * D + e1]); }
+            }
             const float o0 = __fsub_rn(__fmul_rn(x0, c), __fmul_rn(x1, s));
             const float o1 = __fadd_rn(__fmul_rn(x0, s), __fmul_rn(x1, c));
             if (isq) {
-                const int64_t o = ((int64_t)t * H + hh) * D + 2 * ip;
-                if (q_out) { q_out[o] = o0; q_out[o + 1] = o1; }
-                if (q16) { q16[o] = f2h(o0); q16[o + 1] = f2h(o1); }
+                const int64_t o = ((int64_t)t * H + hh) * D;
+                if (q_out) { q_out[o + e0] = o0; q_out[o + e1] = o1; }
+                if (q16) { q16[o + e0] = f2h(o0); q16[o + e1] = f2h(o1); }
             } else {
-                const int64_t o = (int64_t)p * EKV + (int64_t)hh * D + 2 * ip;
-                kc[o] = f2h(o0); kc[o + 1] = f2h(o1);
+                const int64_t o = (int64_t)p * EKV + (int64_t)hh * D;
+                kc[o + e0] = f2h(o0); kc[o + e1] = f2h(o1);
             }
         } else {
             const int e = i - npairs_q - npairs_k;
-            vc[(int64_t)p * EKV + e] = f2h(row[(int64_t)(H + HKV) * D + e]);
+            float v = row[(int64_t)(H + HKV) * D + e];
+            if constexpr (EX) {
+                if (bv) v = __fadd_rn(v, bv[e]);
+            }
+            vc[(int64_t)p * EKV + e] = f2h(v);
         }
     }
 }
@@ -188,6 +202,22 @@ __global__ void k_kv_shift(const uint32_t *__restrict__ kc, const uint32_t *__re
     const uint16_t y0 = f2h(__fsub_rn(__fmul_rn(x0, c.x), __fmul_rn(x1, c.y)));
     const uint16_t y1 = f2h(__fadd_rn(__fmul_rn(x0, c.y), __fmul_rn(x1, c.x)));
     ks[i] = (uint32_t)y0 | ((uint32_t)y1 << 16);
+    vs[i] = vc[i];
+}
+
+// the same in NeoX mode (ggml_compute_forward_rope_f16, mode & GGML_ROPE_TYPE_NEOX): pair ip of a row is elements
+// (ip, ip + D/2); the two f16 values are loaded and stored on their own
+__global__ void k_kv_shift_neox(const uint16_t *__restrict__ kc, const uint32_t *__restrict__ vc, uint16_t *__restrict__ ks,
+                                uint32_t *__restrict__ vs, int64_t npairs, int half_d, const float2 *__restrict__ cs) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npairs) return;
+    const int64_t r = i / half_d;
+    const int ip = (int)(i % half_d);
+    const int64_t e0 = r * 2 * half_d + ip, e1 = e0 + half_d;
+    const float2 c = cs[ip];
+    const float x0 = h2f(kc[e0]), x1 = h2f(kc[e1]);
+    ks[e0] = f2h(__fsub_rn(__fmul_rn(x0, c.x), __fmul_rn(x1, c.y)));
+    ks[e1] = f2h(__fadd_rn(__fmul_rn(x0, c.y), __fmul_rn(x1, c.x)));
     vs[i] = vc[i];
 }
 
@@ -236,24 +266,47 @@ int kcpp_rms_norm_q80t(const float *x, int64_t ldx, const float *w, void *q80t_o
     return 0;
 }
 
-int kcpp_rope_kv(const float *qkv, int64_t ldqkv, float *q_out, uint16_t *q16, uint16_t *kc, uint16_t *vc, int T, int H,
-                 int HKV, int D, int n_past, const int32_t *pos_dev, const void *rope_tab, void *stream) {
+// mode: 0 = NORM pairs, 2 = NeoX pairs (ggml's rope modes); bq / bk / bv: optional f32 biases added to the q / k / v rows
+// before the rotation / the V store (the Qwen2 graph)
+int kcpp_rope_kv_ex(const float *qkv, int64_t ldqkv, float *q_out, uint16_t *q16, uint16_t *kc, uint16_t *vc, int T, int H,
+                    int HKV, int D, int n_past, const int32_t *pos_dev, const void *rope_tab, int mode, const float *bq,
+                    const float *bk, const float *bv, void *stream) {
+    if ((mode != 0 && mode != 2) || D < 2 || D % 2) return -1;
     const int items = H * D / 2 + HKV * D / 2 + HKV * D;
-    hipLaunchKernelGGL(k_rope_kv, dim3((unsigned)T, (unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream, qkv,
-                       ldqkv, q_out, q16, kc, vc, H, HKV, D, n_past, pos_dev, (const float2 *)rope_tab);
+    const dim3 grid((unsigned)T, (unsigned)((items + 255) / 256));
+    if (mode == 0 && !bq && !bk && !bv)
+        hipLaunchKernelGGL(k_rope_kv<false>, grid, dim3(256), 0, (hipStream_t)stream, qkv, ldqkv, q_out, q16, kc, vc, H, HKV, D,
+                           n_past, pos_dev, (const float2 *)rope_tab, 0, (const float *)nullptr, (const float *)nullptr,
+                           (const float *)nullptr);
+    else
+        hipLaunchKernelGGL(k_rope_kv<true>, grid, dim3(256), 0, (hipStream_t)stream, qkv, ldqkv, q_out, q16, kc, vc, H, HKV, D,
+                           n_past, pos_dev, (const float2 *)rope_tab, mode == 2, bq, bk, bv);
     KCPP_CHECK(hipGetLastError());
     return 0;
 }
+int kcpp_rope_kv(const float *qkv, int64_t ldqkv, float *q_out, uint16_t *q16, uint16_t *kc, uint16_t *vc, int T, int H,
+                 int HKV, int D, int n_past, const int32_t *pos_dev, const void *rope_tab, void *stream) {
+    return kcpp_rope_kv_ex(qkv, ldqkv, q_out, q16, kc, vc, T, H, HKV, D, n_past, pos_dev, rope_tab, 0, nullptr, nullptr,
+                           nullptr, stream);
+}
 
-int kcpp_kv_shift_rows(const uint16_t *kc, const uint16_t *vc, uint16_t *ks, uint16_t *vs, int64_t rows, int D,
-                       const float *cs, void *stream) {
-    if (D % 2 || rows < 0) return -1;
+int kcpp_kv_shift_rows_ex(const uint16_t *kc, const uint16_t *vc, uint16_t *ks, uint16_t *vs, int64_t rows, int D,
+                          const float *cs, int mode, void *stream) {
+    if (D % 2 || rows < 0 || (mode != 0 && mode != 2)) return -1;
     const int64_t np = rows * D / 2;
     if (np == 0) return 0;
-    hipLaunchKernelGGL(k_kv_shift, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint32_t *)kc,
-                       (const uint32_t *)vc, (uint32_t *)ks, (uint32_t *)vs, np, D / 2, (const float2 *)cs);
+    if (mode == 2)
+        hipLaunchKernelGGL(k_kv_shift_neox, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, (hipStream_t)stream, kc,
+                           (const uint32_t *)vc, ks, (uint32_t *)vs, np, D / 2, (const float2 *)cs);
+    else
+        hipLaunchKernelGGL(k_kv_shift, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint32_t *)kc,
+                           (const uint32_t *)vc, (uint32_t *)ks, (uint32_t *)vs, np, D / 2, (const float2 *)cs);
     KCPP_CHECK(hipGetLastError());
     return 0;
+}
+int kcpp_kv_shift_rows(const uint16_t *kc, const uint16_t *vc, uint16_t *ks, uint16_t *vs, int64_t rows, int D,
+                       const float *cs, void *stream) {
+    return kcpp_kv_shift_rows_ex(kc, vc, ks, vs, rows, D, cs, 0, stream);
 }
 
 int kcpp_add(float *y, const float *a, const float *b, int64_t n, void *stream) {

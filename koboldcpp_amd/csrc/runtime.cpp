@@ -95,6 +95,7 @@ struct KLayer {
     void *qkv_base = nullptr, *glu_base = nullptr;
     int nqkv = 0;                    // 2: q|k contiguous, 3: q|k|v contiguous
     bool glu_fused = false;
+    float *bq = nullptr, *bk = nullptr, *bv = nullptr;   // q / k / v projection biases (Qwen2), device f32; null: none
 };
 
 struct kcpp_model {
@@ -134,6 +135,7 @@ struct kcpp_model {
     int32_t *moe_rows_h = nullptr;
     float *moe_rw_h = nullptr;
     float2 *rope_tab = nullptr;
+    int rope_mode = 0;                      // 0 = NORM pairs, 2 = NeoX pairs (kcpp_model_set_rope_mode)
     std::vector<float> rope_ff;             // rope frequency factors (rope_freqs.weight); empty: none
     void *kv_scratch = nullptr;             // context shift: moved K/V rows (n_ctx x EKV x 2 f16, lazily)
     float *shift_cs = nullptr;              // context shift: (cos, sin) pairs of the shift distance
@@ -290,8 +292,8 @@ extern "C" int kcpp_model_kv_shift(kcpp_model *m, int p0, int diff, int n_past) 
     RT_CHECK(hipMemcpyAsync(m->shift_cs, row.data(), (size_t)D * 4, hipMemcpyHostToDevice, m->stream));
     uint16_t *ks = (uint16_t *)m->kv_scratch, *vs = ks + (size_t)m->hp.n_ctx * EKV;
     for (auto &L : m->layers) {
-        RC(kcpp_kv_shift_rows(L.kc + (p0 + diff) * EKV, L.vc + (p0 + diff) * EKV, ks, vs, count * HKV, (int)D, m->shift_cs,
-                              m->stream));
+        RC(kcpp_kv_shift_rows_ex(L.kc + (p0 + diff) * EKV, L.vc + (p0 + diff) * EKV, ks, vs, count * HKV, (int)D,
+                                 m->shift_cs, m->rope_mode, m->stream));
         RT_CHECK(hipMemcpyAsync(L.kc + p0 * EKV, ks, (size_t)count * EKV * 2, hipMemcpyDeviceToDevice, m->stream));
         RT_CHECK(hipMemcpyAsync(L.vc + p0 * EKV, vs, (size_t)count * EKV * 2, hipMemcpyDeviceToDevice, m->stream));
     }
@@ -309,6 +311,42 @@ extern "C" int kcpp_model_set_rope_freqs(kcpp_model *m, const float *ff, int n) 
     kcpp_rope_table(tab.data(), m->hp.n_ctx, (int)D, m->hp.rope_base, m->hp.rope_freq_scale, m->rope_ff.data(), 0.0f, 1.0f,
                     32.0f, 1.0f, m->hp.n_ctx);
     RT_CHECK(hipMemcpy(m->rope_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+    return 0;
+}
+
+bool kcpp_model_owns_layer(const kcpp_model *m, int il) { return m && il >= m->il0 && il < m->il1; }
+
+extern "C" int kcpp_model_set_rope_mode(kcpp_model *m, int mode) {
+    if (!m || (mode != 0 && mode != 2)) { g_err = "rope_mode: 0 (NORM) or 2 (NeoX)"; return -1; }
+    RT_CHECK(hipSetDevice(m->device));
+    RT_CHECK(hipStreamSynchronize(m->stream));
+    drop_graphs(m);
+    m->rope_mode = mode;
+    return 0;
+}
+
+extern "C" int kcpp_model_set_qkv_bias(kcpp_model *m, int il, const float *bq, const float *bk, const float *bv) {
+    if (!m || il < m->il0 || il >= m->il1) { g_err = "qkv_bias: not a layer of this stage"; return -1; }
+    const bool any = bq || bk || bv;
+    if (any && !(bq && bk && bv)) { g_err = "qkv_bias: q, k and v biases are all required (or all null)"; return -1; }
+    RT_CHECK(hipSetDevice(m->device));
+    RT_CHECK(hipStreamSynchronize(m->stream));
+    drop_graphs(m);
+    KLayer &L = m->layers[il - m->il0];
+    const int64_t E = m->hp.n_embd, EKV = (int64_t)m->hp.n_head_kv * (E / m->hp.n_head);
+    if (!any) {
+        if (L.bq) (void)hipFree(L.bq);      // one allocation (below)
+        L.bq = L.bk = L.bv = nullptr;
+        return 0;
+    }
+    if (!L.bq) {          // one allocation: bq | bk | bv
+        float *base = nullptr;
+        if (hipMalloc(&base, (size_t)(E + 2 * EKV) * 4) != hipSuccess) { g_err = "qkv_bias alloc"; return -2; }
+        L.bq = base; L.bk = base + E; L.bv = base + E + EKV;
+    }
+    RT_CHECK(hipMemcpy(L.bq, bq, (size_t)E * 4, hipMemcpyHostToDevice));
+    RT_CHECK(hipMemcpy(L.bk, bk, (size_t)EKV * 4, hipMemcpyHostToDevice));
+    RT_CHECK(hipMemcpy(L.bv, bv, (size_t)EKV * 4, hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -541,7 +579,7 @@ extern "C" void kcpp_model_free(kcpp_model *m) {
     F(m->tok_embd.d); F(m->output_norm.d); F(m->output.d); FS(m->output); F(m->output.dec);
     for (auto &L : m->layers) {
         for (auto &t : L.t) { if (t.owned) F(t.d); FS(t); F(t.dec); if (t.pre_owned) F(t.pre); }
-        F(L.qkv_base); F(L.glu_base); F(L.kc); F(L.vc);
+        F(L.qkv_base); F(L.glu_base); F(L.kc); F(L.vc); F(L.bq);
     }
     F(m->hglu); F(m->moe_ids); F(m->moe_w); F(m->moe_rows); F(m->moe_rw); F(m->moe_slots);
     F(m->moe_gx); F(m->moe_gh); F(m->moe_gup); F(m->moe_geo); F(m->moe_gact); F(m->moe_gcnt); F(m->moe_gws);
@@ -1226,6 +1264,39 @@ static int moe_prefill(kcpp_model *m, const KLayer &L, int T) {
     return kcpp_moe_combine(m->x, m->moe_slots, (int64_t)T * E, NU, (int64_t)T * E, s);
 }
 
+// a layer's single-token q|k|v without the fused epilogue: attn_norm, the three mat-vecs into m->qkv, then the bias add,
+// rope and f16 q / K / V stores of kcpp_rope_kv_ex at pos_dev (graph-capturable); t = the layer's decode tensors
+static int qkv_dec_unfused(kcpp_model *m, KLayer &L, const KTensor *t) {
+    const kcpp_hparams &hp = m->hp;
+    const int64_t E = hp.n_embd, H = hp.n_head, HKV = hp.n_head_kv, D = E / H, EKV = HKV * D;
+    hipStream_t s = m->stream;
+    int have = -1;                                   // the activation type m->act holds
+    bool f32_normed = false;
+    for (int j = 1; j <= 3; ++j) {
+        const int vt = kcpp_vec_dot_type(t[j].type);
+        if (vt != have) {
+            if (vt == KT_Q8_K) {
+                RC(kcpp_rms_norm(m->x, E, (const float *)t[0].d, nullptr, E, m->act, E, 1, hp.eps, s));
+            } else {
+                if (!f32_normed) RC(kcpp_rms_norm(m->x, E, (const float *)t[0].d, m->attn, E, nullptr, E, 1, hp.eps, s));
+                f32_normed = true;
+                RC(kcpp_quantize_act(vt, m->attn, E, m->act, E, 1, s));
+            }
+            have = vt;
+        }
+        float *y = m->qkv + (j == 1 ? 0 : (j == 2 ? E : E + EKV));
+        DecArgs a;
+        memset(&a, 0, sizeof a);
+        a.K = E; a.nseg = 1; a.W[0] = (const uint8_t *)t[j].d; a.N[0] = t[j].N; a.Y[0] = y;
+        a.act = (const uint8_t *)m->act;
+        int rc = kcpp_gemv_dec(t[j].type, &a, 0, 0, rows_per_wave(t[j].N, 0), s);
+        if (rc == -3 || rc == -8) rc = kcpp_gemv(t[j].type, t[j].d, nullptr, E, t[j].N, m->act, 1, y, t[j].N, nullptr, 0, 0, s);
+        RC(rc);
+    }
+    return kcpp_rope_kv_ex(m->qkv, E + 2 * EKV, nullptr, m->q16, L.kc, L.vc, 1, (int)H, (int)HKV, (int)D, 0, m->pos_dev,
+                           m->rope_tab, m->rope_mode, L.bq, L.bk, L.bv, s);
+}
+
 // single-token layer step, 6-7 launches (gemv_dec.hip fusions); position read from m->pos_dev
 static int forward_layers_dec(kcpp_model *m) {
     const kcpp_hparams &hp = m->hp;
@@ -1251,19 +1322,28 @@ static int forward_layers_dec(kcpp_model *m) {
             a.K = E; a.x = m->x; a.nw = (const float *)t[0].d; a.eps = hp.eps;
             a.q16 = m->q16; a.kc = L.kc; a.vc = L.vc; a.ekv = EKV; a.D = (int)D; a.pos = m->pos_dev;
             a.rope_tab = m->rope_tab;
+            a.rope_neox = m->rope_mode == 2;
             const int ty = t[j].type;
             while (j <= 3 && t[j].type == ty) {
                 a.W[a.nseg] = (const uint8_t *)t[j].d; a.N[a.nseg] = t[j].N; a.role[a.nseg] = j - 1;
+                a.bias[a.nseg] = j == 1 ? L.bq : (j == 2 ? L.bk : L.bv);
                 ++a.nseg; ++j;
             }
             qty[nq++] = ty;
         }
-        int mixed_rc = -3;
-        if (nq == 2 && qty[0] == KT_Q4_K_RS && qty[1] == KT_Q6_K_RS && qa[0].nseg == 2 && qa[1].nseg == 1 &&
+        // q|k|v bias / NeoX pairs (Qwen2): the RS kernels carry them; a launch answering -3 (another weight type, a K
+        // beyond the register-resident shapes) sends the layer's q|k|v through the unfused ops, inside the same graph
+        const bool ex = m->rope_mode != 0 || L.bq;
+        bool unfused = false;
+        if (ex)
+            for (int i = 0; i < nq; ++i)
+                unfused |= !(qty[i] == KT_Q4_K_RS || qty[i] == KT_Q5_K_RS || qty[i] == KT_Q6_K_RS);
+        int mixed_rc = unfused ? 0 : -3;
+        if (!unfused && nq == 2 && qty[0] == KT_Q4_K_RS && qty[1] == KT_Q6_K_RS && qa[0].nseg == 2 && qa[1].nseg == 1 &&
             qa[1].role[0] == 2) {
             // q|k Q4_K + v Q6_K (Q4_K_M "more bits" layers): one launch (gemv_rs.hip k_gemv_rs_qkv)
             DecArgs c = qa[0];
-            c.W[2] = qa[1].W[0]; c.N[2] = qa[1].N[0]; c.role[2] = 2; c.nseg = 3;
+            c.W[2] = qa[1].W[0]; c.N[2] = qa[1].N[0]; c.role[2] = 2; c.bias[2] = qa[1].bias[0]; c.nseg = 3;
             mixed_rc = kcpp_gemv_rs_qkv_mixed(&c, s);
             if (mixed_rc != -3 && mixed_rc != -5) RC(mixed_rc);
         }
@@ -1273,7 +1353,12 @@ static int forward_layers_dec(kcpp_model *m) {
             if (mixed_rc != -3 && mixed_rc != -5) RC(mixed_rc);
         }
         if (mixed_rc != 0)
-            for (int i = 0; i < nq; ++i) RC(kcpp_gemv_dec(qty[i], &qa[i], 2, 1, 2, s));
+            for (int i = 0; i < nq && !unfused; ++i) {
+                const int rc = kcpp_gemv_dec(qty[i], &qa[i], 2, 1, 2, s);
+                if (rc == -3 && ex) unfused = true;       // (a launch before it wrote what the unfused ops write again)
+                else RC(rc);
+            }
+        if (unfused) RC(qkv_dec_unfused(m, L, t));
         // --- attention over the cache (f32 output); wo quantizes it in its own prologue (PRO 2: the Q8_K /
         // Q8_0 conversion overlaps wo's first weight loads instead of ending the attention combine; measured
         // against the combine quantizing and wo copying: 572 vs 575 tok/s, within noise)
@@ -1393,7 +1478,7 @@ static int forward_layers(kcpp_model *m, int T, int n_past, bool dev_pos) {
             if (m->lanes.empty()) {
                 const void *Wq[3] = {t[1].d, t[2].d, t[3].d};
                 const int64_t Nq[3] = {E, EKV, EKV};
-                if (m->kv_tk == KT_F16) {          // rope + the f16 K/V stores in the GEMM's epilogue
+                if (m->kv_tk == KT_F16 && m->rope_mode == 0 && !L.bq) {   // rope + the f16 K/V stores in the GEMM's epilogue
                     RC(kcpp_gemm_q80t_qkv_rope(Wq, Nq, E, m->act, T, m->rope_tab, n_past, posp, (int)D, m->q16, L.kc,
                                                L.vc, m->gemm_ws, s));
                     roped = true;
@@ -1420,10 +1505,12 @@ static int forward_layers(kcpp_model *m, int T, int n_past, bool dev_pos) {
         }
         const bool kvq = m->kv_tk != KT_F16;
         if (kvq) {   // quantized cache: f32 rope in place, quantize K/V rows into the cache, Q8_0-dot attention
-            RC(kcpp_rope_qk_inplace(m->qkv, LQ, T, (int)H, (int)HKV, (int)D, n_past, posp, m->rope_tab, s));
+            RC(kcpp_rope_qk_inplace_ex(m->qkv, LQ, T, (int)H, (int)HKV, (int)D, n_past, posp, m->rope_tab, m->rope_mode, L.bq,
+                                       L.bk, L.bv, s));
             RC(kcpp_kv_store_q(m->kv_tk, m->kv_tv, m->qkv, LQ, E, E + EKV, T, EKV, L.kc, L.vc, hp.n_ctx, n_past, posp, s));
         } else if (!roped) {
-            RC(kcpp_rope_kv(m->qkv, LQ, nullptr, m->q16, L.kc, L.vc, T, (int)H, (int)HKV, (int)D, n_past, posp, m->rope_tab, s));
+            RC(kcpp_rope_kv_ex(m->qkv, LQ, nullptr, m->q16, L.kc, L.vc, T, (int)H, (int)HKV, (int)D, n_past, posp, m->rope_tab,
+                               m->rope_mode, L.bq, L.bk, L.bv, s));
         }
         const bool woq = kcpp_vec_dot_type(t[4].type) == KT_Q8_K && !m->fa_exact && !kvq;
         // Q8_0 tile layout, ubatch > 16: attention writes attn_output's KT_Q8_0_TA activation itself (keys split

@@ -59,6 +59,11 @@ _SIGS = {
     "kcpp_moe_route_norm": [P, I64, P, Fl, P, I, I64, I, I, P, P, I, P],
     "kcpp_model_kv_shift": [P, I, I, I],
     "kcpp_rope_kv": [P, I64, P, P, P, P, I, I, I, I, I, P, P, P],
+    "kcpp_rope_kv_ex": [P, I64, P, P, P, P, I, I, I, I, I, P, P, I, P, P, P, P],
+    "kcpp_kv_shift_rows_ex": [P, P, P, P, I64, I, P, I, P],
+    "kcpp_rope_qk_inplace_ex": [P, I64, I, I, I, I, I, P, P, I, P, P, P, P],
+    "kcpp_model_set_rope_mode": [P, I],
+    "kcpp_model_set_qkv_bias": [P, I, P, P, P],
     "kcpp_flash_attn": [P, P, P, P, P, P, I, I, I, I, I, P, I, Fl, I, P],
     "kcpp_flash_attn_prefill_mfma": [P, P, P, P, I, I, I, I, I, Fl, P],
     "kcpp_flash_attn_prefill_mfma_ex": [P, P, P, P, P, P, I, I, I, I, I, Fl, P],
@@ -229,7 +234,8 @@ class DecArgs(ctypes.Structure):
                 ("act", P), ("x", P), ("nw", P), ("eps", Fl), ("res", P), ("q16", P), ("kc", P), ("vc", P),
                 ("ekv", I64), ("D", I), ("pos", P), ("rope_tab", P), ("eid", P), ("ebytes", I64), ("escale", P),
                 ("act_mtot", I64), ("act_col", I64), ("n_exp", I64), ("pre", P), ("eid1", P),
-                ("route_w", P), ("route_wt", I), ("route_ne", I), ("route_ids", P), ("route_wts", P)]
+                ("route_w", P), ("route_wt", I), ("route_ne", I), ("route_ids", P), ("route_wts", P),
+                ("bias", P * 3), ("rope_neox", I)]
 
 
 if ctypes.sizeof(DecArgs) != _L.kcpp_gemv_dec_args_size():
@@ -367,6 +373,22 @@ class Model:
         import numpy as np
         a = np.ascontiguousarray(ff, dtype=np.float32)
         _chk(_L.kcpp_model_set_rope_freqs(self.m, a.ctypes.data_as(P), len(a)), "set_rope_freqs")
+
+    def set_rope_mode(self, mode):
+        """0 = NORM pairs (Llama, the default), 2 = NeoX pairs (Qwen2)"""
+        _chk(_L.kcpp_model_set_rope_mode(self.m, int(mode)), "set_rope_mode")
+
+    def set_qkv_bias(self, il, bq, bk, bv):
+        """q / k / v projection biases of layer il (float32 n_embd, n_embd_gqa, n_embd_gqa); all None clears them"""
+        import numpy as np
+        arrs = [None if b is None else np.ascontiguousarray(b, dtype=np.float32) for b in (bq, bk, bv)]
+        hp = self.hp
+        ekv = hp["n_head_kv"] * (hp["n_embd"] // hp["n_head"])
+        for a, n in zip(arrs, (hp["n_embd"], ekv, ekv)):
+            if a is not None and a.size != n:
+                raise ValueError("set_qkv_bias: expected %d values, got %d" % (n, a.size))
+        _chk(_L.kcpp_model_set_qkv_bias(self.m, int(il), *[None if a is None else a.ctypes.data_as(P) for a in arrs]),
+             "set_qkv_bias")
 
     def set_fa_exact(self, on):
         """strict-parity attention (reference order, f16 accumulation); see kcpp_flash_attn_exact"""
