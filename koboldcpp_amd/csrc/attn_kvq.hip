@@ -278,21 +278,19 @@ __global__ void __launch_bounds__(256) k_fa_q(const float *__restrict__ q, int64
             mx = max16_f(mx);
             const float mnew = fmaxf(m[r], mx);
             const float alpha = (mnew == -INFINITY) ? 1.0f : expf(m[r] - mnew);
-            float ls = 0.0f;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                s[r][j] = (s[r][j] == -INFINITY) ? 0.0f : expf(s[r][j] - mnew);
-                ls += s[r][j];
-            }
-            ls += dpp_f<0xB1>(ls); ls += dpp_f<0x4E>(ls); ls += dpp_f<0x141>(ls); ls += dpp_f<0x140>(ls);
-            l[r] = l[r] * alpha + ls;
+            for (int j = 0; j < 4; ++j) s[r][j] = (s[r][j] == -INFINITY) ? 0.0f : expf(s[r][j] - mnew);
+            l[r] *= alpha;
             m[r] = mnew;
 #pragma unroll
             for (int j = 0; j < DPT; ++j) o[r][j] *= alpha;
         }
-        for (int src = 0; src < 16; ++src) {
+        // keys in ascending order, and the row sum l beside O from the same broadcast weights (every thread of the row
+        // group holds it): the order of the reference's loop over the keys (ggml.c:15748-15851: S = S * ms + vs and
+        // ggml_vec_mad_f32 per key), so that the f32 sums over thousands of keys round as the reference's do
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
+        for (int j = 0; j < 4; ++j) {
+            for (int src = 0; src < 16; ++src) {
                 const int kr = src + 16 * j;
                 float vr[DPT];
 #pragma unroll
@@ -300,6 +298,7 @@ __global__ void __launch_bounds__(256) k_fa_q(const float *__restrict__ q, int64
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float pr = __shfl(s[r][j], ((16 * ty) & 63) + src, 64);
+                    l[r] += pr;
 #pragma unroll
                     for (int e = 0; e < DPT; ++e) o[r][e] = fmaf(pr, vr[e], o[r][e]);
                 }
