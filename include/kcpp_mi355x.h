@@ -231,7 +231,8 @@ int kcpp_fa_decode_ex(const uint16_t *q16, const uint16_t *kc, const uint16_t *v
 /* diagnostic: per-workgroup phase stamps of the split-KV decode kernel (s_memrealtime, 8 per workgroup) into p
  * (device, or NULL to disable); tools only */
 void kcpp_fa_set_stamps(void *p);
-/* the MFMA prefill kernel alone (koboldcpp_amd/csrc/attn_mfma.hip); -3 when the shape is not covered */
+/* the MFMA prefill kernel alone (koboldcpp_amd/csrc/attn_mfma.hip): D = 128, H = G HKV with G = 1..8; -3 when the
+ * shape is not covered */
 int kcpp_flash_attn_prefill_mfma(const uint16_t *q16, const uint16_t *kc, const uint16_t *vc, float *out, int T, int H,
                                  int HKV, int D, int n_past, float scale, void *stream);
 /* the same with, for T <= 64 and ws (kcpp_fa_workspace_bytes, zero before first use), the keys split over ~512
@@ -240,6 +241,14 @@ int kcpp_flash_attn_prefill_mfma(const uint16_t *q16, const uint16_t *kc, const 
 int kcpp_flash_attn_prefill_mfma_ex(const uint16_t *q16, const uint16_t *kc, const uint16_t *vc, float *out, void *qta,
                                     void *ws, int T, int H, int HKV, int D, int n_past, float scale, void *stream);
 int64_t kcpp_fa_split_ws_bytes(int H);
+/* Launch plan of the prefill attention at D = 128 (host only, no GPU; csrc/fa_plan.h).  out = {kernel: 0 FMA tiles
+ * (k_fa_prefill<128>), 1 MFMA unsplit, 2 MFMA key-split + merge, as the auto path (kcpp_flash_attn force_path 0; the
+ * model's Q8_0-tile branch, which has the workspace) chooses it for H / HKV; heads per workgroup; query blocks per
+ * workgroup; workgroups per split; splits; 64-key tiles per split; merge grid; partial bytes used behind the workspace
+ * header}.  Fields 1..7 describe the MFMA launch (what the direct entries and force_path 3 run) also where field 0 is 0.
+ * KCPP_FA_PREFILL_MFMA=0 (environment, read once) sends every ratio but 4 to the FMA tiles.  -3: D != 128, H % HKV,
+ * H / HKV > 8. */
+int kcpp_fa_prefill_plan(int T, int H, int HKV, int D, int n_past, int have_ws, int32_t out[8]);
 /* single-token decode attention (the k_fa_dec5 + k_fa_comb4 pair) with the combine writing the KT_Q8_0_TA activation of
  * the token (qta) -- bit-identical to kcpp_quantize_act(KT_Q8_0_TA) of its f32 output; n_kv_max = the caches' row count
  * when n_past_dev is given (the graph-replayable form); -3 = not covered */

@@ -8,8 +8,10 @@
 // kernel with half accumulators; this is a wave64 split-KV design instead:
 //   decode  : k_fa_decode  grid (chunks of 256 keys, kv-head, query) -> partial (O, m, l)
 //             k_fa_combine one 256-thread block per (query, head pair) -> f32 out (+Q8_K quant)
-//   prefill : k_fa_prefill tiled 64 queries x 64 keys per step, online softmax.
+//   prefill : k_fa_prefill tiled 64 queries x 64 keys per step, online softmax; at D = 128 the auto path gives the
+//             GQA ratios of fa_plan.h's table to the matrix-core kernel of attn_mfma.hip instead.
 #include "attn_dec.h"
+#include "fa_plan.h"
 #include "kcpp_common.h"
 #include "kcpp_internal.h"
 #include "gemv_units.h"
@@ -814,9 +816,10 @@ int kcpp_flash_attn(const uint16_t *q16, const uint16_t *kc, const uint16_t *vc,
         return 0;
     }
     if (!out) return -2;
-    // prefill: MFMA kernel (attn_mfma.hip) for GQA groups of 4 (force_path 3, or auto), else FMA tiles (2)
+    // prefill: MFMA kernel (attn_mfma.hip; GQA ratios 1..8) for force_path 3, and in the auto path for the ratios
+    // fa_plan.h's table turns on; else FMA tiles (2)
     int rc = -3;
-    if (force_path == 3 || force_path == 0)
+    if (force_path == 3 || (force_path == 0 && fa_prefill_mfma_auto(G0)))
         rc = kcpp_flash_attn_prefill_mfma(q16, kc, vc, out, T, H, HKV, D, n_past, scale, stream);
     if (rc == -3 && force_path == 3) return -3;
     if (rc == -3)

@@ -3,8 +3,10 @@
 // Same operator as k_fa_prefill (GGML_OP_FLASH_ATTN_EXT, ggml.c:15667; causal mask, f16 K/V cache,
 // Q rounded to f16): softmax(Q K^T * scale) V with an online softmax over 64-key tiles.
 //
-// Work split: one workgroup = one KV head x 16 queries; its 4 waves are the 4 query heads of the
-// GQA group (Llama-3: 32 q heads / 8 kv heads), so every K/V tile staged in LDS serves 4 heads.
+// Work split: one workgroup = one KV head and four SLOTS of (one query head, 16 queries), so every K/V tile staged in
+// LDS serves 4 x 16 queries.  k_fa_prefill_mfma / _mfma2 (A/B forms, H = 4 HKV only): the 4 waves are the 4 query heads
+// of the GQA group over one 16-query block (Llama-3: 32 q heads / 8 kv heads).  k_fa_prefill_mfma3 (production), GQA
+// ratios G = 1..8: the slots are GH = 4, 2 or 1 heads x 4 / GH consecutive 16-query blocks (fa_plan.h).
 // Per wave and 64-key tile:
 //   S^T = K . Q^T     (keys x queries)  16 MFMAs: A = K rows from LDS, B = this wave's Q (registers)
 //                      -> C layout: lane holds query (lane & 15) and keys 4(lane>>4)+r of each
@@ -17,6 +19,7 @@
 // (ggml_vec_mad_f16), so this stays inside the path's f16 tolerance.
 #include "kcpp_common.h"
 #include "kcpp_internal.h"
+#include "fa_plan.h"     // FM_Q, FM_K, the split constants, the launch plan
 
 #include <algorithm>
 #include <cstdlib>
@@ -24,12 +27,6 @@
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef float f4 __attribute__((ext_vector_type(4)));
 
-#define FM_Q 16          // queries per workgroup
-#define FM_K 64          // keys per tile
-#define FM_SPLIT_T 64    // key-split prefill (k_fa_prefill_mfma3<8, true>): ubatches up to this many tokens,
-#define FM_SPLITS 32     // at most this many key splits
-#define FM_PQ 132        // split partial of one (query, head): 128 dims, m, l, pad
-#define FM_PS (16 * FM_PQ)
 #define FM_KP 136        // K tile row pitch (halves): 128 + 8 -> rows 272 B apart (bank spread)
 #define FM_VP 72         // V^T tile row pitch (halves): 64 + 8
 
@@ -312,11 +309,19 @@ __device__ __forceinline__ void fa_dma16(const void *g, const void *lds_base) {
 }
 __device__ __forceinline__ int fa_swz(int row, int c) { return row * 16 + (c ^ ((row & 7) << 1)); }
 
-// NW = 8: two waves per query head, wave w (head w & 3) takes key half hf = w >> 2 of every 64-key tile (2 waves per
+// NW = 8: two waves per slot, wave w (slot w & 3) takes key half hf = w >> 2 of every 64-key tile (2 waves per
 // SIMD so one's softmax runs under the other's MFMAs); the halves share each tile's maximum through LDS, so P and the
 // running max are v3's, and their (l, O) partial sums are added at the end (only the f32 summation order differs).
 //
-// SPL (short ubatches, BASELINE config 3's 32 tokens: (T / 16) x HKV workgroups alone leave most CUs idle): the grid
+// G (template, default 4): the GQA ratio H / HKV.  GH = 4 (G % 4 == 0), 2 (G % 2 == 0) or 1 heads per workgroup over
+// QB = 4 / GH consecutive 16-query blocks; slot s = head hk G + GH gsub + s % GH, query block QB qbg + s / GH; GS = G / GH
+// workgroups (gsub) share a kv head and a query group.  G = 4 is GH = 4, QB = 1, GS = 1: the kernel as it was (its code
+// differs from the pre-template one by two independent scalar instructions exchanged in the prologue).  The variants NW = 4
+// and HM are built for G = 4 only.  -Rpass-analysis=kernel-resource-usage, <8, SPL, false, G>: unsplit 144 VGPRs, 48
+// SGPRs at every G; split 143 VGPRs, 50 (G = 4), 51 (8), 52 (1, 2), 53 (3, 5, 6, 7) SGPRs; LDS 131584 B, no scratch,
+// 2 waves / SIMD in all of them -- G = 4's figures are the pre-template kernel's.
+//
+// SPL (short ubatches, BASELINE config 3's 32 tokens: (T / 16) x (H / 4) workgroups alone leave most CUs idle): the grid
 // also splits the keys, ch tiles per workgroup; each split stores its unnormalised (O, m, l) per query and head and
 // k_fa_split_merge (next launch) merges the splits in split order.  (An in-launch merge by the last-arriving split
 // -- write-through partials, a ticket, device-coherent loads -- measured 15-30 us per layer at 2-16 splits against
@@ -329,40 +334,46 @@ __device__ __forceinline__ int fa_swz(int row, int c) { return row * 16 + (c ^ (
 // at the end as before.  tools/fa_ab.py at 512 queries: 16.3 -> 14.7 us (n_past 0), 45.6 -> 41.6 (1536), 79.4 -> 73.3
 // (3328), within the kernel test's error bars -- but as the default it took the tiny Q4_1 model's logits just past
 // 1.5x the reference's own spread (tests/test_kquants_low.py: 0.0291 vs 0.0283), so variant 4 stays the default
-template <int NW, bool SPL, bool HM = false>
+template <int NW, bool SPL, bool HM = false, int G = 4>
 __global__ void __launch_bounds__(64 * NW, 1) k_fa_prefill_mfma3(const uint16_t *__restrict__ q16,
                                                                 const uint16_t *__restrict__ kc,
                                                                 const uint16_t *__restrict__ vc, float *__restrict__ out,
                                                                 int T, int H, int HKV, int n_past, float scale,
                                                                 float *__restrict__ part, unsigned *__restrict__ tick,
                                                                 int ch, int nsp_grid, uint8_t *__restrict__ qta) {
-    constexpr int D = 128, G = 4, NST = 4;
+    constexpr int D = 128, NST = 4;
+    constexpr int GH = G % 4 == 0 ? 4 : (G % 2 == 0 ? 2 : 1), GS = G / GH, QB = 4 / GH;   // fa_plan.h
     constexpr int NB = NW == 8 ? 2 : 4;               // 16-key blocks per wave and tile
     __shared__ __attribute__((aligned(16))) uint4 sk[NST][FM_K * 16];
     __shared__ __attribute__((aligned(16))) uint4 sv[NST][FM_K * 16];
-    __shared__ float s_mx[2][4][16];                  // NW = 8: per key half, head and query: the tile maximum
+    __shared__ float s_mx[2][4][16];                  // NW = 8: per key half, slot and query: the tile maximum
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int hf = NW == 8 ? wave >> 2 : 0;
+    const int slot = wave & 3;                        // (head, query block) of the workgroup's four
     // 1-D grid, XCD-aware: blocks b and b + 8 share an XCD, so kv head = b % 8 (+ 8 (b / 8 % (HKV / 8))) keeps every
     // query block of one head on one XCD -- its K/V (n_keys x 512 B) stays in that XCD's L2 instead of every XCD
     // streaming all heads from the Infinity Cache
     int bid = blockIdx.x, sp = 0;
     if constexpr (SPL) {
-        const int nb0 = (T + FM_Q - 1) / FM_Q * HKV;
+        const int nb0 = ((T + FM_Q - 1) / FM_Q + QB - 1) / QB * HKV * GS;
         sp = bid / nb0;
         bid -= sp * nb0;                              // nb0 % 8 == 0 when HKV % 8 == 0: a head keeps its XCD
     }
-    int hk, qb;
+    // (HKV % 8 != 0: blocks of kv head hk sit on the XCDs congruent to hk mod gcd(8, HKV) -- HKV = 4, Qwen2.5-7B: two
+    // XCDs per head, one head per XCD).  The GS workgroups that share (hk, query blocks) follow hk, so they share its XCD
+    int hk, wq;                                       // wq = qbg GS + gsub
     if (HKV % 8 == 0) {
         const int j = bid >> 3;
         hk = (bid & 7) + 8 * (j % (HKV / 8));
-        qb = j / (HKV / 8);
+        wq = j / (HKV / 8);
     } else {
         hk = bid % HKV;
-        qb = bid / HKV;
+        wq = bid / HKV;
     }
-    const int q0 = qb * FM_Q, h = hk * G + (wave & 3);
+    const int qbg = wq / GS, gsub = wq - qbg * GS;
+    const int qb = qbg * QB + slot / GH;              // this slot's query block
+    const int q0 = qb * FM_Q, h = hk * G + gsub * GH + slot % GH;
     const int EKV = HKV * D;
     const int ql = lane & 15, g = lane >> 4;
     const int qi = q0 + ql;
@@ -379,7 +390,11 @@ __global__ void __launch_bounds__(64 * NW, 1) k_fa_prefill_mfma3(const uint16_t 
 #pragma unroll
     for (int i = 0; i < 8; ++i) o[i] = f4{0.f, 0.f, 0.f, 0.f};
     float m_run = -INFINITY, l_run = 0.0f;
-    const int n_keys = n_past + min(q0 + FM_Q, T);
+    // keys any query of the WORKGROUP can see (its last query block): the tile loop, the DMA clamp and the length
+    // mask are the workgroup's; the diagonal (qpos, qmin) is the slot's.  A slot of an earlier query block meets tiles
+    // wholly past its diagonal: every S masked, mt = -inf in both key halves, m_new = m_run, alpha = 1, P = 0 (also
+    // when m_run is still -inf: see alpha below), so o and l stay as they were bit for bit
+    const int n_keys = n_past + min((qbg * QB + QB) * FM_Q, T);
     const int ntile = (n_keys + FM_K - 1) / FM_K;
     int kt0 = 0, kt1 = ntile;                             // this workgroup's key tiles
     if constexpr (SPL) {
@@ -387,7 +402,7 @@ __global__ void __launch_bounds__(64 * NW, 1) k_fa_prefill_mfma3(const uint16_t 
         kt1 = min(kt0 + ch, ntile);
         if (kt0 >= ntile) return;                         // past this query block's keys (whole workgroup)
     }
-    const int qmin = n_past + q0;                         // smallest query position of the block
+    const int qmin = n_past + q0;                         // smallest query position of the slot's block
     // DMA: wave w fetches key rows (64 / NW) w .. +64/NW of the tile (instructions of 4 rows) for K and for V;
     // lane: row 4 i + (lane >> 4) of the instruction, chunk slot lane & 15 <- global chunk (slot ^ 2 (row & 7))
     constexpr int RPW = FM_K / NW, IPW = RPW / 4;
@@ -484,12 +499,13 @@ __global__ void __launch_bounds__(64 * NW, 1) k_fa_prefill_mfma3(const uint16_t 
         if constexpr (NW == 8 && !HM) {
             // both key halves take the whole tile's maximum (exchanged through LDS), so P, alpha and the running max
             // are v3's exactly; only the f32 summation of O and l is split in two
-            if (g == 0) s_mx[hf][wave & 3][ql] = mt;
+            if (g == 0) s_mx[hf][slot][ql] = mt;
             __syncthreads();
-            mt = fmaxf(mt, s_mx[hf ^ 1][wave & 3][ql]);
+            mt = fmaxf(mt, s_mx[hf ^ 1][slot][ql]);
         }
         const float m_new = fmaxf(m_run, mt);
-        // m_new = -inf only when every key so far is masked (a half-tile wholly past the diagonal): keep alpha 1
+        // m_new = -inf only when every key so far is masked (a half-tile, or for a slot of an earlier query block or
+        // of a later key split a whole tile, wholly past the diagonal): keep alpha 1
         const float alpha = m_new == -INFINITY ? 1.0f : __builtin_amdgcn_exp2f(m_run - m_new);
         float ls = 0.0f;
         h8 pb[NB / 2];
@@ -532,7 +548,7 @@ __global__ void __launch_bounds__(64 * NW, 1) k_fa_prefill_mfma3(const uint16_t 
     }
     if constexpr (NW == 8) {
         // merge the two key halves: wave hf = 1 publishes (m, l, O) in the (now idle) K ring, wave hf = 0 combines
-        float *xo = (float *)&sk[0][0] + (wave & 3) * (16 * 130);     // [16 queries][128 dims + m + l]
+        float *xo = (float *)&sk[0][0] + slot * (16 * 130);           // [16 queries][128 dims + m + l]
         if (hf == 1) {
 #pragma unroll
             for (int db = 0; db < 8; ++db)
@@ -559,9 +575,12 @@ __global__ void __launch_bounds__(64 * NW, 1) k_fa_prefill_mfma3(const uint16_t 
         }
     }
     if constexpr (SPL) {
-        // publish this split's unnormalised (O, m, l) per query and head; k_fa_split_merge (the next launch) merges
-        if (hf == 0) {
-            float *pp = part + (((int64_t)(qb * HKV + hk) * nsp_grid + sp) * 4 + (wave & 3)) * FM_PS + ql * FM_PQ;
+        // publish this split's unnormalised (O, m, l) per query and head; k_fa_split_merge (the next launch) merges.
+        // partials: [workgroup of split 0 = (qbg HKV + hk) GS + gsub][split][slot].  A slot whose query block has no key
+        // in this split (an earlier block of the workgroup) publishes (O = 0, m = -inf, l = 0); the merge never reads it
+        // (its nsp is the query block's own).  Slots wholly past T publish nothing and have no merge workgroup
+        if (hf == 0 && (QB == 1 || q0 < T)) {
+            float *pp = part + (((int64_t)((qbg * HKV + hk) * GS + gsub) * nsp_grid + sp) * 4 + slot) * FM_PS + ql * FM_PQ;
 #pragma unroll
             for (int db = 0; db < 8; ++db) *(float4 *)(pp + 16 * db + 4 * g) = make_float4(o[db][0], o[db][1], o[db][2], o[db][3]);
             if (g == 0) *(float4 *)(pp + 128) = make_float4(m_run, l_run, 0.0f, 0.0f);
@@ -615,18 +634,23 @@ extern "C" int kcpp_fa_prefill_set_variant(int v) {
     return old;
 }
 
-// merge of the key splits (SPL): one workgroup per (query block, kv head, head of the group), thread = (query,
+// merge of the key splits (SPL): one workgroup per slot of the split kernel's workgroups, thread = (query,
 // 8-dim chunk); the splits' (m, l) and O chunks loaded together, weights exp2(m_s - max), summed in split order;
 // out f32 and / or the KT_Q8_0_TA activation (a Q8_0 block = 4 threads' 32 dims, k_quant_q80's rounding)
+template <int G = 4>
 __global__ void __launch_bounds__(256) k_fa_split_merge(const float *__restrict__ part, float *__restrict__ out,
                                                         uint8_t *__restrict__ qta, int T, int H, int HKV, int n_past,
                                                         int ch, int nsp_grid) {
-    constexpr int D = 128, G = 4;
-    const int slot = blockIdx.x >> 2, mh = blockIdx.x & 3, qb = slot / HKV, hk = slot % HKV;
+    constexpr int D = 128;
+    constexpr int GH = G % 4 == 0 ? 4 : (G % 2 == 0 ? 2 : 1), GS = G / GH, QB = 4 / GH;   // fa_plan.h
+    // slot = the split kernel's workgroup (qbg HKV + hk) GS + gsub, mh = its slot
+    const int slot = blockIdx.x >> 2, mh = blockIdx.x & 3, qbg = slot / (HKV * GS), hk = slot / GS % HKV, gsub = slot % GS;
+    const int qb = qbg * QB + mh / GH;
     const int tid = threadIdx.x, mq = tid >> 4, dc = tid & 15;
     const int q0 = qb * FM_Q;
+    if (QB > 1 && q0 >= T) return;                        // a slot wholly past T: nothing was published
     const int n_keys = n_past + min(q0 + FM_Q, T);
-    const int nsp = ((n_keys + FM_K - 1) / FM_K + ch - 1) / ch;
+    const int nsp = ((n_keys + FM_K - 1) / FM_K + ch - 1) / ch;   // the splits that hold keys of THIS query block
     const float *pm = part + ((int64_t)slot * nsp_grid * 4 + mh) * FM_PS + mq * FM_PQ;
     auto at = [&](int k) { return pm + (int64_t)min(k, nsp - 1) * 4 * FM_PS; };   // branch-free: clamped + weight 0
     float mk[FM_SPLITS], lk[FM_SPLITS];
@@ -671,7 +695,7 @@ __global__ void __launch_bounds__(256) k_fa_split_merge(const float *__restrict_
                 ov[4 * c + 3] = ov[4 * c + 3] + v[j][c].w * w;
             }
     }
-    const int qi = q0 + mq, h = hk * G + mh;
+    const int qi = q0 + mq, h = hk * G + gsub * GH + mh % GH;
     if (qi >= T) return;                                  // (a query's 16 threads leave together)
     const float inv = 1.0f / lsum;
 #pragma unroll
@@ -705,47 +729,83 @@ __global__ void __launch_bounds__(256) k_fa_split_merge(const float *__restrict_
 }
 
 // the key-split variant's workspace (kcpp_fa_workspace_bytes reserves it, after the 2 KB header):
-// [query block][kv head][split < FM_SPLITS][4 heads][16 queries][FM_PQ] partials for T <= FM_SPLIT_T
+// [workgroup of one split][split < FM_SPLITS][4 slots][16 queries][FM_PQ] partials for T <= FM_SPLIT_T: at most
+// FM_SPLIT_T / FM_Q query blocks x H heads of (query block, head) slots at any ratio
 extern "C" int64_t kcpp_fa_split_ws_bytes(int H) {
-    return KCPP_FA_WS_HEADER + (int64_t)(FM_SPLIT_T / FM_Q) * (H / 4) * FM_SPLITS * 4 * FM_PS * 4;
+    return KCPP_FA_WS_HEADER + (int64_t)(FM_SPLIT_T / FM_Q) * H * FM_SPLITS * FM_PS * 4;
 }
 
+// out = {kernel, heads per workgroup, query blocks per workgroup, workgroups per split, splits, tiles per split, merge
+// grid, partial bytes} (fa_plan.h FaPrefillPlan), as the auto path chooses the kernel
+extern "C" int kcpp_fa_prefill_plan(int T, int H, int HKV, int D, int n_past, int have_ws, int32_t out[8]) {
+    FaPrefillPlan p;
+    const int rc = fa_prefill_plan(T, H, HKV, D, n_past, have_ws != 0, false, &p);
+    if (rc) return rc;
+    const int32_t v[8] = {p.kernel, p.gh, p.qb, p.nb0, p.nsp, p.ch, p.merge_grid, (int32_t)p.part_bytes};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return 0;
+}
+
+// variant 4 (the default) at ratio G: the plan's grid, ch and nsp
+template <int G>
+static int fa_mfma3_run(const FaPrefillPlan &p, const uint16_t *q16, const uint16_t *kc, const uint16_t *vc, float *out,
+                        uint8_t *qta, void *ws, int T, int H, int HKV, int n_past, float scale, hipStream_t s) {
+    if (p.nsp > 1) {
+        float *part = (float *)((uint8_t *)ws + KCPP_FA_WS_HEADER);
+        hipLaunchKernelGGL((k_fa_prefill_mfma3<8, true, false, G>), dim3(p.nb0 * p.nsp), dim3(512), 0, s, q16, kc, vc, out,
+                           T, H, HKV, n_past, scale, part, (unsigned *)nullptr, p.ch, p.nsp, (uint8_t *)nullptr);
+        KCPP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(k_fa_split_merge<G>, dim3(p.merge_grid), dim3(256), 0, s, part, out, qta, T, H, HKV, n_past,
+                           p.ch, p.nsp);
+    } else {
+        hipLaunchKernelGGL((k_fa_prefill_mfma3<8, false, false, G>), dim3(p.nb0), dim3(512), 0, s, q16, kc, vc, out, T, H,
+                           HKV, n_past, scale, (float *)nullptr, (unsigned *)nullptr, 0, 1, qta);
+    }
+    KCPP_CHECK(hipGetLastError());
+    return 0;
+}
+
+static int fa_mfma3_run_g(const FaPrefillPlan &p, const uint16_t *q16, const uint16_t *kc, const uint16_t *vc, float *out,
+                          uint8_t *qta, void *ws, int T, int H, int HKV, int n_past, float scale, hipStream_t s) {
+    switch (H / HKV) {
+#define KCPP_FM_CASE(GG) \
+    case GG: return fa_mfma3_run<GG>(p, q16, kc, vc, out, qta, ws, T, H, HKV, n_past, scale, s);
+        KCPP_FM_CASE(1)
+        KCPP_FM_CASE(2)
+        KCPP_FM_CASE(3)
+        KCPP_FM_CASE(4)
+        KCPP_FM_CASE(5)
+        KCPP_FM_CASE(6)
+        KCPP_FM_CASE(7)
+        KCPP_FM_CASE(8)
+#undef KCPP_FM_CASE
+    }
+    return -3;
+}
+
+// kcpp_fa_prefill_set_variant's numbers other than 4 (1, 2: the v1 / v2 kernels, 3: four waves, 5: HM) are A/B
+// forms of G = 4 alone; every other ratio runs variant 4 whatever the number
 extern "C" int kcpp_flash_attn_prefill_mfma_ex(const uint16_t *q16, const uint16_t *kc, const uint16_t *vc, float *out,
                                                void *qta, void *ws, int T, int H, int HKV, int D, int n_past, float scale,
                                                void *stream) {
-    if (D != 128 || HKV <= 0 || H != 4 * HKV || (!out && !qta)) return -3;
-    const int v = g_fa_prefill_variant ? g_fa_prefill_variant : 4;
-    const int nqb = (T + FM_Q - 1) / FM_Q;
-    const int nb0 = nqb * HKV;
-    if ((v == 4 || v == 5) && ws && T <= FM_SPLIT_T && nb0 <= 512) {
-        // keys split so that the grid has ~512 workgroups (at most FM_SPLITS splits of whole 64-key tiles)
-        const int ntile = (n_past + T + FM_K - 1) / FM_K;
-        const int want = std::min(FM_SPLITS, std::max(1, 512 / nb0));
-        const int ch = (ntile + want - 1) / want;
-        const int nsp = (ntile + ch - 1) / ch;
-        if (nsp > 1) {
+    if (!out && !qta) return -3;
+    const int v = (g_fa_prefill_variant && HKV > 0 && H == 4 * HKV) ? g_fa_prefill_variant : 4;
+    FaPrefillPlan p;
+    if (fa_prefill_plan(T, H, HKV, D, n_past, ws && (v == 4 || v == 5), true, &p)) return -3;
+    if (v == 4) return fa_mfma3_run_g(p, q16, kc, vc, out, (uint8_t *)qta, ws, T, H, HKV, n_past, scale, (hipStream_t)stream);
+    if (v == 5) {
+        if (p.nsp > 1) {
             float *part = (float *)((uint8_t *)ws + KCPP_FA_WS_HEADER);
-            if (v == 5)
-                hipLaunchKernelGGL((k_fa_prefill_mfma3<8, true, true>), dim3(nb0 * nsp), dim3(512), 0, (hipStream_t)stream,
-                                   q16, kc, vc, out, T, H, HKV, n_past, scale, part, (unsigned *)nullptr, ch, nsp,
-                                   (uint8_t *)nullptr);
-            else
-                hipLaunchKernelGGL((k_fa_prefill_mfma3<8, true>), dim3(nb0 * nsp), dim3(512), 0, (hipStream_t)stream, q16, kc,
-                                   vc, out, T, H, HKV, n_past, scale, part, (unsigned *)nullptr, ch, nsp, (uint8_t *)nullptr);
+            hipLaunchKernelGGL((k_fa_prefill_mfma3<8, true, true>), dim3(p.nb0 * p.nsp), dim3(512), 0, (hipStream_t)stream,
+                               q16, kc, vc, out, T, H, HKV, n_past, scale, part, (unsigned *)nullptr, p.ch, p.nsp,
+                               (uint8_t *)nullptr);
             KCPP_CHECK(hipGetLastError());
-            hipLaunchKernelGGL(k_fa_split_merge, dim3(nb0 * 4), dim3(256), 0, (hipStream_t)stream, part, out, (uint8_t *)qta,
-                               T, H, HKV, n_past, ch, nsp);
-            KCPP_CHECK(hipGetLastError());
-            return 0;
+            hipLaunchKernelGGL(k_fa_split_merge<4>, dim3(p.merge_grid), dim3(256), 0, (hipStream_t)stream, part, out,
+                               (uint8_t *)qta, T, H, HKV, n_past, p.ch, p.nsp);
+        } else {
+            hipLaunchKernelGGL((k_fa_prefill_mfma3<8, false, true>), dim3(p.nb0), dim3(512), 0, (hipStream_t)stream, q16, kc,
+                               vc, out, T, H, HKV, n_past, scale, (float *)nullptr, (unsigned *)nullptr, 0, 1, (uint8_t *)qta);
         }
-    }
-    if (v == 4 || v == 5) {
-        if (v == 5)
-            hipLaunchKernelGGL((k_fa_prefill_mfma3<8, false, true>), dim3(nb0), dim3(512), 0, (hipStream_t)stream, q16, kc, vc,
-                               out, T, H, HKV, n_past, scale, (float *)nullptr, (unsigned *)nullptr, 0, 1, (uint8_t *)qta);
-        else
-            hipLaunchKernelGGL((k_fa_prefill_mfma3<8, false>), dim3(nb0), dim3(512), 0, (hipStream_t)stream, q16, kc, vc, out,
-                               T, H, HKV, n_past, scale, (float *)nullptr, (unsigned *)nullptr, 0, 1, (uint8_t *)qta);
         KCPP_CHECK(hipGetLastError());
         return 0;
     }
@@ -755,20 +815,17 @@ extern "C" int kcpp_flash_attn_prefill_mfma_ex(const uint16_t *q16, const uint16
 
 extern "C" int kcpp_flash_attn_prefill_mfma(const uint16_t *q16, const uint16_t *kc, const uint16_t *vc, float *out,
                                             int T, int H, int HKV, int D, int n_past, float scale, void *stream) {
-    if (D != 128 || HKV <= 0 || H != 4 * HKV) return -3;
-    const int v = g_fa_prefill_variant ? g_fa_prefill_variant : 4;
+    const int v = (g_fa_prefill_variant && HKV > 0 && H == 4 * HKV) ? g_fa_prefill_variant : 4;
+    FaPrefillPlan p;
+    if (fa_prefill_plan(T, H, HKV, D, n_past, false, true, &p)) return -3;
+    if (v == 4)
+        return fa_mfma3_run_g(p, q16, kc, vc, out, (uint8_t *)nullptr, nullptr, T, H, HKV, n_past, scale, (hipStream_t)stream);
     if (v == 3)
-        hipLaunchKernelGGL((k_fa_prefill_mfma3<4, false>), dim3((T + FM_Q - 1) / FM_Q * HKV), dim3(256), 0,
-                           (hipStream_t)stream, q16, kc, vc, out, T, H, HKV, n_past, scale, (float *)nullptr,
-                           (unsigned *)nullptr, 0, 1, (uint8_t *)nullptr);
-    else if (v == 4)
-        hipLaunchKernelGGL((k_fa_prefill_mfma3<8, false>), dim3((T + FM_Q - 1) / FM_Q * HKV), dim3(512), 0,
-                           (hipStream_t)stream, q16, kc, vc, out, T, H, HKV, n_past, scale, (float *)nullptr,
-                           (unsigned *)nullptr, 0, 1, (uint8_t *)nullptr);
+        hipLaunchKernelGGL((k_fa_prefill_mfma3<4, false>), dim3(p.nb0), dim3(256), 0, (hipStream_t)stream, q16, kc, vc, out,
+                           T, H, HKV, n_past, scale, (float *)nullptr, (unsigned *)nullptr, 0, 1, (uint8_t *)nullptr);
     else if (v == 5)
-        hipLaunchKernelGGL((k_fa_prefill_mfma3<8, false, true>), dim3((T + FM_Q - 1) / FM_Q * HKV), dim3(512), 0,
-                           (hipStream_t)stream, q16, kc, vc, out, T, H, HKV, n_past, scale, (float *)nullptr,
-                           (unsigned *)nullptr, 0, 1, (uint8_t *)nullptr);
+        hipLaunchKernelGGL((k_fa_prefill_mfma3<8, false, true>), dim3(p.nb0), dim3(512), 0, (hipStream_t)stream, q16, kc, vc,
+                           out, T, H, HKV, n_past, scale, (float *)nullptr, (unsigned *)nullptr, 0, 1, (uint8_t *)nullptr);
     else if (v == 1)
         hipLaunchKernelGGL(k_fa_prefill_mfma, dim3((T + FM_Q - 1) / FM_Q, HKV), dim3(256), 0, (hipStream_t)stream, q16, kc,
                            vc, out, T, H, HKV, n_past, scale);

@@ -27,6 +27,7 @@
 
 #include "../../include/kcpp_mi355x.h"
 #include "../../include/kcpp_synth.h"
+#include "fa_plan.h"
 #include "kcpp_internal.h"
 
 static thread_local std::string g_err;
@@ -1517,7 +1518,9 @@ static int forward_layers(kcpp_model *m, int T, int n_past, bool dev_pos) {
         // over the grid for short ubatches)
         bool attn_q = false;
         // (row-split lanes too: attention is not split, and wo's lanes read the same activation)
-        if (m->q80t && !kvq && !m->fa_exact && t[4].type == KT_Q8_0_T && (T == 1 || (T > 16 && !posp))) {
+        // (prefill: at the GQA ratios fa_plan.h's table gives the MFMA kernel; the others quantize after kcpp_flash_attn)
+        if (m->q80t && !kvq && !m->fa_exact && t[4].type == KT_Q8_0_T &&
+            (T == 1 || (T > 16 && !posp && D == 128 && fa_prefill_mfma_auto((int)(H / HKV))))) {
             const int rc = T == 1 ? kcpp_flash_attn_dec_ta(m->q16, L.kc, L.vc, nullptr, m->act, m->fa_ws, (int)H, (int)HKV,
                                                            (int)D, n_past, posp, hp.n_ctx, kq_scale, s)
                                   : kcpp_flash_attn_prefill_mfma_ex(m->q16, L.kc, L.vc, nullptr, m->act, m->fa_ws, T,

@@ -68,6 +68,7 @@ _SIGS = {
     "kcpp_flash_attn_prefill_mfma": [P, P, P, P, I, I, I, I, I, Fl, P],
     "kcpp_flash_attn_prefill_mfma_ex": [P, P, P, P, P, P, I, I, I, I, I, Fl, P],
     "kcpp_fa_split_ws_bytes": [I],
+    "kcpp_fa_prefill_plan": [I, I, I, I, I, I, P],
     "kcpp_flash_attn_dec_ta": [P, P, P, P, P, P, I, I, I, I, P, I, Fl, P],
     "kcpp_fa_decode_ex": [P, P, P, I64, I64, P, P, P, I, I, I, P, I, Fl, I, P],
     "kcpp_fa_set_stamps": [P],
@@ -474,6 +475,23 @@ def gemm_plan(t, K, N, M, mode=0, bs_aligned=True):
     _chk(_L.kcpp_gemm_plan(int(t), int(K), int(N), int(M), int(mode), int(bool(bs_aligned)), out), "gemm_plan")
     d = dict(zip(("family", "rs", "tile", "waves", "ks", "xg", "pf", "nwg"), out))
     d["family"] = GEMM_FAMILY[d["family"]]
+    return d
+
+
+FA_PREFILL_KERNEL = ("fma", "mfma", "mfma_split")
+
+
+def fa_prefill_plan(T, H, HKV, D=128, n_past=0, have_ws=False):
+    """what the prefill attention launches at D = 128 (kcpp_fa_prefill_plan; host only): dict of kernel (a
+    FA_PREFILL_KERNEL name, as the auto path chooses), gh / qb (heads / 16-query blocks per workgroup), nb0 (workgroups
+    per split), nsp, ch (64-key tiles per split), merge_grid, part_bytes; None for a shape the MFMA kernel does not cover"""
+    out = (ctypes.c_int32 * 8)()
+    rc = _L.kcpp_fa_prefill_plan(int(T), int(H), int(HKV), int(D), int(n_past), int(bool(have_ws)), out)
+    if rc == -3:
+        return None
+    _chk(rc, "fa_prefill_plan")
+    d = dict(zip(("kernel", "gh", "qb", "nb0", "nsp", "ch", "merge_grid", "part_bytes"), out))
+    d["kernel"] = FA_PREFILL_KERNEL[d["kernel"]]
     return d
 
 
