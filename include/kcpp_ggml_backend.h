@@ -52,7 +52,8 @@ enum kggml_op {
 };
 /* ggml/include/ggml.h:541-558 */
 enum kggml_unary_op {
-    KGGML_UNARY_OP_ABS = 0, KGGML_UNARY_OP_NEG = 2, KGGML_UNARY_OP_RELU = 6, KGGML_UNARY_OP_SILU = 10
+    KGGML_UNARY_OP_ABS = 0, KGGML_UNARY_OP_NEG = 2, KGGML_UNARY_OP_TANH = 4, KGGML_UNARY_OP_RELU = 6, KGGML_UNARY_OP_GELU = 8,
+    KGGML_UNARY_OP_SILU = 10
 };
 /* ggml/include/ggml.h:331-336 */
 enum kggml_status { KGGML_STATUS_ALLOC_FAILED = -2, KGGML_STATUS_FAILED = -1, KGGML_STATUS_SUCCESS = 0 };

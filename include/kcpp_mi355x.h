@@ -200,6 +200,10 @@ int kcpp_flash_attn_exact(const uint16_t *q16, const uint16_t *kc, const uint16_
 int kcpp_flash_attn_ext_exact(const float *q, int64_t q_nb1, int64_t q_nb2, const uint16_t *kc, const uint16_t *vc,
                               const uint16_t *mask, int64_t mask_ld, float *out, int T, int H, int HKV, int D, int n_kv,
                               float scale, void *stream);
+/* the same with the op's logit soft-cap (see kcpp_flash_attn_ext_sc); D = 64 (no cap), 128 or 256 */
+int kcpp_flash_attn_ext_exact_sc(const float *q, int64_t q_nb1, int64_t q_nb2, const uint16_t *kc, const uint16_t *vc,
+                                 const uint16_t *mask, int64_t mask_ld, float *out, int T, int H, int HKV, int D,
+                                 int n_kv, float scale, void *stream, float logit_softcap);
 /* quantized KV cache (koboldcpp --quantkv 1/2 = q8_0/q4_0 K and V, gpttype_adapter.cpp:1958-1959; attn_kvq.hip).
  * Per-layer cache layout: Q8_0 = qs int8 [n_ctx][ekv] ++ d f16 [n_ctx][ekv/32]; Q4_0 = qs [n_ctx][ekv/2] (ggml
  * nibble order per 32-block) ++ d f16 [n_ctx][ekv/32].  kcpp_kv_cache_bytes(KT_F16 / KT_Q8_0 / KT_Q4_0, ...). */
@@ -285,13 +289,17 @@ typedef struct kcpp_tdesc {
     int64_t nb[4];
 } kcpp_tdesc;
 enum { KCPP_BIN_ADD = 0, KCPP_BIN_SUB = 1, KCPP_BIN_MUL = 2, KCPP_BIN_DIV = 3 };
-enum { KCPP_UN_SILU = 0, KCPP_UN_SCALE = 1, KCPP_UN_NEG = 2, KCPP_UN_RELU = 3 };
+enum { KCPP_UN_SILU = 0, KCPP_UN_SCALE = 1, KCPP_UN_NEG = 2, KCPP_UN_RELU = 3, KCPP_UN_GELU = 4, KCPP_UN_TANH = 5 };
 /* d = a (op) b, b broadcast over d's shape by modulo (ggml_can_repeat) */
 int kcpp_ggml_binary(int op, const void *a, const kcpp_tdesc *ta, const void *b, const kcpp_tdesc *tb, void *d,
                      const kcpp_tdesc *td, void *stream);
-/* d = f(a); KCPP_UN_SCALE multiplies by param */
+/* d = f(a); KCPP_UN_SCALE multiplies by param.  KCPP_UN_GELU is the reference CPU's table form (ggml.c:2564-2578:
+ * 0 at x <= -10, x at x >= 10, else table[f16(x)]), bit-equal to it; KCPP_UN_TANH is tanhf per element */
 int kcpp_ggml_unary(int op, const void *a, const kcpp_tdesc *ta, void *d, const kcpp_tdesc *td, float param,
                     void *stream);
+/* builds the 65,536-entry f16 GELU table on the host (libm tanhf, the reference's ggml_init loop) and uploads it to
+ * the current device, once; the ggml backend calls it at initialisation, kcpp_ggml_unary on first use otherwise */
+int kcpp_ggml_gelu_table_init(void);
 /* element-order copy with conversion (KT_F32 / KT_F16 each side); shapes may differ, counts equal */
 int kcpp_ggml_cpy(int stype, const void *src, const kcpp_tdesc *ts, int dtype, void *dst, const kcpp_tdesc *td,
                   void *stream);
@@ -326,8 +334,8 @@ int kcpp_ggml_get_rows(int stype, const void *src, const kcpp_tdesc *ts, const i
 int kcpp_ggml_mul_mat_f(int wtype, const void *w, const kcpp_tdesc *tw, const float *x, const kcpp_tdesc *tx, float *d,
                         const kcpp_tdesc *td, void *stream);
 /* GGML_OP_FLASH_ATTN_EXT in the graph's own form: q f32 (byte strides q_nb1 per query, q_nb2 per head), K/V f16
- * cache views [n_kv][HKV][128], optional f16 mask [T][n_kv] (row stride mask_ld; -inf keys skipped), out f32
- * [T][H][128]; ws of kcpp_fa_ext_workspace_bytes */
+ * cache views [n_kv][HKV][D], optional f16 mask [T][n_kv] (row stride mask_ld; -inf keys skipped), out f32
+ * [T][H][D]; ws of kcpp_fa_ext_workspace_bytes (D <= 128: 128 floats per partial; D = 256: the decode pair's) */
 int64_t kcpp_fa_ext_workspace_bytes(int T, int H, int n_kv, int D);
 /* f32 row moves (the MoE mat-mul's gather / scatter): dst row i <- src row i, K floats, each side addressed by byte
  * offsets (offs != NULL) or by a byte stride (ld) */
@@ -336,6 +344,17 @@ int kcpp_rows_move_f32(const void *src, const int64_t *soffs, int64_t sld, void 
 int kcpp_flash_attn_ext(const float *q, int64_t q_nb1, int64_t q_nb2, const uint16_t *kc, const uint16_t *vc,
                         const uint16_t *mask, int64_t mask_ld, float *out, void *ws, int T, int H, int HKV, int D,
                         int n_kv, float scale, void *stream);
+/* the same with the op's logit soft-cap (op_params[2], Gemma-2): s = cap * tanhf(q.k * scale / cap), then the mask
+ * (ggml.c:15738-15740, 15804-15810); logit_softcap 0 = none, and then the functions above bit for bit.  D = 64 (no
+ * cap), 128 or 256 (attn_d256.hip: a split decode pair up to 16 queries, an MFMA tile kernel beyond); the D = 256
+ * views are [n_kv][HKV][256] and out [T][H][256].  _dec_sc: one query on the split decode kernels, key j of kv head h
+ * at kc + j k_ld + h k_hs elements, q heads q_nb2 bytes apart; -3 = shape not covered (take kcpp_flash_attn_ext_sc) */
+int kcpp_flash_attn_ext_sc(const float *q, int64_t q_nb1, int64_t q_nb2, const uint16_t *kc, const uint16_t *vc,
+                           const uint16_t *mask, int64_t mask_ld, float *out, void *ws, int T, int H, int HKV, int D,
+                           int n_kv, float scale, void *stream, float logit_softcap);
+int kcpp_flash_attn_ext_dec_sc(const float *q, int64_t q_nb2, const uint16_t *kc, const uint16_t *vc, int64_t k_ld,
+                               int64_t k_hs, const uint16_t *mask, float *out, void *ws, int H, int HKV, int D, int n_kv,
+                               float scale, void *stream, float logit_softcap);
 /* the same over quantized K / V views (--quantkv): tk / tv = KT_Q8_0 / KT_Q4_0, views of ggml blocks at byte strides
  * nb1 (position) / nb2 (kv head); q quantized to Q8_0 per 32-block and integer block dots, V dequantized, f32
  * accumulation (ggml_compute_forward_flash_attn_ext_f16's quantized branch, ggml.c:15748-15851); D 64 or 128 */

@@ -10,6 +10,8 @@
 //             k_fa_combine one 256-thread block per (query, head pair) -> f32 out (+Q8_K quant)
 //   prefill : k_fa_prefill tiled 64 queries x 64 keys per step, online softmax; at D = 128 the auto path gives the
 //             GQA ratios of fa_plan.h's table to the matrix-core kernel of attn_mfma.hip instead.
+// The ggml-op (graph) form at the end of the file also takes the op's logit soft-cap (template flag CAP of the
+// kernels it runs) and hands head dim 256 to attn_d256.hip.
 #include "attn_dec.h"
 #include "fa_plan.h"
 #include "kcpp_common.h"
@@ -32,13 +34,14 @@ static void *g_fa_stamps = nullptr;       // diagnostic stamp buffer (tools only
 // row (no cross-lane reduction).  Partials (O, m, l) per chunk, merged by k_fa_combine (the role of the
 // reference's flash_attn_combine_results, ggml/src/ggml-cuda/fattn-common.cuh:523).  Used for 2..16
 // queries (single-token decode runs k_fa_dec4) and by the ggml-op form.
-template <int D, int G>
+// CAP (graph form only): scale = the op's scale / cap and the score is cap * tanhf(dot * scale) before the mask
+template <int D, int G, bool CAP = false>
 __global__ void __launch_bounds__(256) k_fa_decode(const uint16_t *__restrict__ q16, const uint16_t *__restrict__ kc,
                                                    const uint16_t *__restrict__ vc, float *__restrict__ part_o,
                                                    float2 *__restrict__ part_ml, int T, int H,
                                                    int HKV, int n_past_arg, const int32_t *__restrict__ n_past_dev,
                                                    int n_chunks, float scale, const uint16_t *__restrict__ mask,
-                                                   int64_t mask_ld, int64_t kv_ld, int64_t kv_hs) {
+                                                   int64_t mask_ld, int64_t kv_ld, int64_t kv_hs, float cap = 0.0f) {
     static_assert(D == 128, "head dim 128");
     const int c = blockIdx.x, hk = blockIdx.y, t = blockIdx.z;
     const int n_past = n_past_dev ? n_past_dev[0] : n_past_arg;
@@ -93,7 +96,10 @@ __global__ void __launch_bounds__(256) k_fa_decode(const uint16_t *__restrict__ 
             sc += dpp_f<0xB1>(sc); sc += dpp_f<0x4E>(sc); sc += dpp_f<0x141>(sc); sc += dpp_f<0x140>(sc);
             if (sub == 0) {
                 float sv = -INFINITY;
-                if (p < p1) sv = mrow ? (mrow[p] == 0xFC00 ? -INFINITY : sc * scale + h2f(mrow[p])) : sc * scale;
+                if constexpr (CAP) {
+                    const float cs = cap * tanhf(sc * scale);
+                    if (p < p1) sv = mrow ? (mrow[p] == 0xFC00 ? -INFINITY : cs + h2f(mrow[p])) : cs;
+                } else if (p < p1) sv = mrow ? (mrow[p] == 0xFC00 ? -INFINITY : sc * scale + h2f(mrow[p])) : sc * scale;
                 s_sc[g][p - p0] = sv;
             }
         }
@@ -223,20 +229,23 @@ __global__ void __launch_bounds__(256) k_fa_dec4(const uint16_t *__restrict__ q1
 // floats), rounded to f16 in the kernel; the f16 mask row added to the scores, -inf keys skipped.
 // FINAL (short contexts, NS = 1, kcpp_flash_attn force_path 7): one workgroup per kv head walks every key and writes
 // the attention output itself (part_o = out [H][128]) -- no combine launch
-template <int G, bool NT, int NW = 4, bool GRAPH = false, bool FINAL = false>
+// CAP (with GRAPH): the op's logit soft-cap; scale = the op's scale / cap, the score cap * tanhf(dot * scale) + mask
+template <int G, bool NT, int NW = 4, bool GRAPH = false, bool FINAL = false, bool CAP = false>
 __global__ void __launch_bounds__(64 * NW) k_fa_dec5(const uint16_t *__restrict__ q16, const uint16_t *__restrict__ kc,
                                                      const uint16_t *__restrict__ vc, float *__restrict__ part_o,
                                                      float2 *__restrict__ part_ml, int H, int n_past_arg,
                                                      const int32_t *__restrict__ n_past_dev, int NS, float scale,
                                                      int64_t kv_ld, int64_t kv_hs, int n_rows,
                                                      const float *__restrict__ qf = nullptr, int64_t qf_hs = 0,
-                                                     const uint16_t *__restrict__ mask = nullptr) {
+                                                     const uint16_t *__restrict__ mask = nullptr, float cap = 0.0f) {
+    static_assert(!CAP || GRAPH, "the soft-cap exists in the graph form only");
     constexpr int D = 128, CK = 16 * NW;              // keys per chunk: 16 per wave
     const int sp = blockIdx.x, hk = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int sub = lane & 15, kq = lane >> 4;
     __shared__ fadec::Smem<G, NW> sm;
-    const float sc2 = scale * 1.4426950408889634f;    // scores in the exp2 domain
+    const float sc2 = CAP ? scale : scale * 1.4426950408889634f;    // scores in the exp2 domain (CAP: after tanhf)
+    const float cap2 = cap * 1.4426950408889634f;
     uint4 qraw[GRAPH ? 1 : G];
     float4 qfa[GRAPH ? G : 1], qfb[GRAPH ? G : 1];
 #pragma unroll
@@ -287,12 +296,14 @@ __global__ void __launch_bounds__(64 * NW) k_fa_dec5(const uint16_t *__restrict_
         const int b0 = CK * c + 16 * wave;
         float md[4];
         if constexpr (GRAPH) madd(ma, md);
-        if (b0 < nkv) fadec::consume(st, b0, nkv, kq, sc2, ka, va, GRAPH ? md : nullptr);
+        if constexpr (CAP) { if (b0 < nkv) fadec::consume<G, true>(st, b0, nkv, kq, sc2, ka, va, md, cap2); }
+        else if (b0 < nkv) fadec::consume(st, b0, nkv, kq, sc2, ka, va, GRAPH ? md : nullptr);
         issue(CK * (c + 2 * NS) + 16 * wave, lim, ka, va, ma);
         if (c + NS >= nch) break;
         const int b1 = CK * (c + NS) + 16 * wave;
         if constexpr (GRAPH) madd(mb, md);
-        if (b1 < nkv) fadec::consume(st, b1, nkv, kq, sc2, kn, vn, GRAPH ? md : nullptr);
+        if constexpr (CAP) { if (b1 < nkv) fadec::consume<G, true>(st, b1, nkv, kq, sc2, kn, vn, md, cap2); }
+        else if (b1 < nkv) fadec::consume(st, b1, nkv, kq, sc2, kn, vn, GRAPH ? md : nullptr);
         issue(CK * (c + 3 * NS) + 16 * wave, lim, kn, vn, mb);
     }
     fadec::finish<G, NW, FINAL>(st, sm, hk, sp, NS, part_o, part_ml);
@@ -597,12 +608,13 @@ __global__ void __launch_bounds__(1024) k_fa_combine(const float *__restrict__ p
 #define FP_BK 64
 // D = 128 or 64 (TinyLlama-class heads): thread tx owns DPT = D / 16 output dims; n_past from n_past_dev when given
 // (single-token decode replayed from a graph)
-template <int D>
+// CAP (explicit mask form only): scale = the op's scale / cap, the score cap * tanhf(dot * scale) before the mask
+template <int D, bool CAP = false>
 __global__ void __launch_bounds__(256) k_fa_prefill(const uint16_t *__restrict__ q16, const uint16_t *__restrict__ kc,
                                                     const uint16_t *__restrict__ vc, float *__restrict__ out, int T,
                                                     int H, int HKV, int n_past_arg, float scale,
                                                     const uint16_t *__restrict__ mask, int64_t mask_ld, int n_kv,
-                                                    const int32_t *__restrict__ n_past_dev) {
+                                                    const int32_t *__restrict__ n_past_dev, float cap = 0.0f) {
     constexpr int DPT = D / 16;
     const int n_past = n_past_dev ? n_past_dev[0] : n_past_arg;
     const int qt = blockIdx.x, h = blockIdx.y;
@@ -677,7 +689,8 @@ __global__ void __launch_bounds__(256) k_fa_prefill(const uint16_t *__restrict__
                 if (expl) {
                     const uint16_t mv = (qi < T && p < kend) ? (mask ? mask[(int64_t)qi * mask_ld + p] : (uint16_t)0)
                                                              : (uint16_t)0xFC00;
-                    s[r][j] = mv == 0xFC00 ? -INFINITY : s[r][j] * scale + h2f(mv);
+                    if constexpr (CAP) s[r][j] = mv == 0xFC00 ? -INFINITY : cap * tanhf(s[r][j] * scale) + h2f(mv);
+                    else s[r][j] = mv == 0xFC00 ? -INFINITY : s[r][j] * scale + h2f(mv);
                 } else {
                     s[r][j] = (qi < T && p <= qpos) ? s[r][j] * scale : -INFINITY;
                 }
@@ -901,9 +914,14 @@ int kcpp_fa_decode_ex(const uint16_t *q16, const uint16_t *kc, const uint16_t *v
 // one query of GGML_OP_FLASH_ATTN_EXT in the graph form (the b1 backend's decode): k_fa_dec5<GRAPH> over the views
 // (key j of kv head h at kc + j k_ld + h k_hs elements), the f16 mask row (may be null), q f32 [H][D] with head
 // stride q_nb2 bytes rounded to f16 in the kernel, then k_fa_comb4 into out [H][D].  -3: shape not covered.
-int kcpp_flash_attn_ext_dec(const float *q, int64_t q_nb2, const uint16_t *kc, const uint16_t *vc, int64_t k_ld,
-                            int64_t k_hs, const uint16_t *mask, float *out, void *ws, int H, int HKV, int D, int n_kv,
-                            float scale, void *stream) {
+// logit_softcap != 0 (op_params[2], Gemma-2): s = cap * tanhf(q.k * scale / cap) before the mask.  D = 256: the
+// kernels of attn_d256.hip.
+int kcpp_flash_attn_ext_dec_sc(const float *q, int64_t q_nb2, const uint16_t *kc, const uint16_t *vc, int64_t k_ld,
+                               int64_t k_hs, const uint16_t *mask, float *out, void *ws, int H, int HKV, int D, int n_kv,
+                               float scale, void *stream, float logit_softcap) {
+    if (D == 256)
+        return kcpp_fa256_dec(q, 0, q_nb2, kc, vc, k_ld, k_hs, mask, 0, out, ws, 1, H, HKV, n_kv, scale, logit_softcap,
+                              stream);
     if (D != 128 || H % HKV || H % 2 || n_kv < 1 || q_nb2 % 16 || ((uintptr_t)q & 15)) return -3;
     const int G = H / HKV, NS = fa4_splits(HKV);
     if (!(G == 1 || G == 2 || G == 4 || G == 8)) return -3;
@@ -914,13 +932,27 @@ int kcpp_flash_attn_ext_dec(const float *q, int64_t q_nb2, const uint16_t *kc, c
 #define KCPP_FAD(GG)                                                                                                \
     hipLaunchKernelGGL((k_fa_dec5<GG, true, 4, true>), dim3(NS, HKV), dim3(256), 0, s, (const uint16_t *)nullptr, kc, vc, \
                        po, pml, H, n_kv - 1, (const int32_t *)nullptr, NS, scale, k_ld, k_hs, n_kv, q, q_nb2 / 4, mask)
-    switch (G) {
-    case 1: KCPP_FAD(1); break;
-    case 2: KCPP_FAD(2); break;
-    case 4: KCPP_FAD(4); break;
-    default: KCPP_FAD(8); break;
+#define KCPP_FADC(GG)                                                                                               \
+    hipLaunchKernelGGL((k_fa_dec5<GG, true, 4, true, false, true>), dim3(NS, HKV), dim3(256), 0, s,                  \
+                       (const uint16_t *)nullptr, kc, vc, po, pml, H, n_kv - 1, (const int32_t *)nullptr, NS,        \
+                       scale / logit_softcap, k_ld, k_hs, n_kv, q, q_nb2 / 4, mask, logit_softcap)
+    if (logit_softcap != 0.0f) {
+        switch (G) {
+        case 1: KCPP_FADC(1); break;
+        case 2: KCPP_FADC(2); break;
+        case 4: KCPP_FADC(4); break;
+        default: KCPP_FADC(8); break;
+        }
+    } else {
+        switch (G) {
+        case 1: KCPP_FAD(1); break;
+        case 2: KCPP_FAD(2); break;
+        case 4: KCPP_FAD(4); break;
+        default: KCPP_FAD(8); break;
+        }
     }
 #undef KCPP_FAD
+#undef KCPP_FADC
     KCPP_CHECK(hipGetLastError());
     switch (NS) {
 #define KCPP_FAC(N_) case N_: hipLaunchKernelGGL((k_fa_comb4<0, N_>), dim3(H / 2), dim3(256), 0, s, po, pml, out, (uint8_t *)nullptr, \
@@ -932,6 +964,11 @@ int kcpp_flash_attn_ext_dec(const float *q, int64_t q_nb2, const uint16_t *kc, c
     KCPP_CHECK(hipGetLastError());
     return 0;
 }
+int kcpp_flash_attn_ext_dec(const float *q, int64_t q_nb2, const uint16_t *kc, const uint16_t *vc, int64_t k_ld,
+                            int64_t k_hs, const uint16_t *mask, float *out, void *ws, int H, int HKV, int D, int n_kv,
+                            float scale, void *stream) {
+    return kcpp_flash_attn_ext_dec_sc(q, q_nb2, kc, vc, k_ld, k_hs, mask, out, ws, H, HKV, D, n_kv, scale, stream, 0.0f);
+}
 
 // GGML_OP_FLASH_ATTN_EXT as the ggml graph states it (the b1 backend path): q f32 [D][T][H] with byte
 // strides (q_nb1 between queries, q_nb2 between heads), K/V f16 cache views [n_kv][HKV][D] (row stride
@@ -939,6 +976,7 @@ int kcpp_flash_attn_ext_dec(const float *q, int64_t q_nb2, const uint16_t *kc, c
 // [T][H][D].  Q is rounded to f16 first (q_to_vec_dot of ggml_compute_forward_flash_attn_ext_f16,
 // ggml.c:15667); keys whose mask is -inf are skipped.  ws: kcpp_fa_workspace_bytes(T, H, n_kv) + T*H*D*2.
 int64_t kcpp_fa_ext_workspace_bytes(int T, int H, int n_kv, int D) {
+    if (D > 128) return kcpp_fa256_ws_bytes(T, H);      // 256 floats per partial (attn_d256.hip)
     return ((kcpp_fa_workspace_bytes(T, H, n_kv) + 255) & ~(int64_t)255) + (int64_t)T * H * D * 2 + 256;
 }
 
@@ -949,11 +987,28 @@ __global__ void k_q_to_f16(const char *__restrict__ q, int64_t nb1, int64_t nb2,
         q16[((int64_t)t * H + h) * D + d] = f2h(((const float *)(q + t * nb1 + h * nb2))[d]);
 }
 
-int kcpp_flash_attn_ext(const float *q, int64_t q_nb1, int64_t q_nb2, const uint16_t *kc, const uint16_t *vc,
-                        const uint16_t *mask, int64_t mask_ld, float *out, void *ws, int T, int H, int HKV, int D,
-                        int n_kv, float scale, void *stream) {
+// logit_softcap != 0 (D = 128 or 256): s = cap * tanhf(q.k * scale / cap) before the mask (ggml.c:15738-15810)
+int kcpp_flash_attn_ext_sc(const float *q, int64_t q_nb1, int64_t q_nb2, const uint16_t *kc, const uint16_t *vc,
+                           const uint16_t *mask, int64_t mask_ld, float *out, void *ws, int T, int H, int HKV, int D,
+                           int n_kv, float scale, void *stream, float logit_softcap) {
     hipStream_t s = (hipStream_t)stream;
+    if (D == 256) {
+        if (H % HKV || n_kv < 1 || T < 1) return -1;
+        if (mask_ld < 0) mask_ld = 0;
+        // up to 16 queries: the split decode kernel, one grid plane per query; more: the MFMA tile kernel
+        // (a GQA ratio the decode kernel is not built for: the tile kernel, which takes any)
+        if (T <= 16) {
+            const int rc = kcpp_fa256_dec(q, q_nb1, q_nb2, kc, vc, (int64_t)HKV * 256, 256, mask, mask_ld, out, ws, T, H,
+                                          HKV, n_kv, scale, logit_softcap, stream);
+            if (rc != -3) return rc;
+        }
+        return kcpp_fa256_prefill(q, q_nb1, q_nb2, kc, vc, mask, mask_ld, out, T, H, HKV, n_kv, scale, logit_softcap,
+                                  stream);
+    }
     if ((D != 128 && D != 64) || H % HKV || H / HKV > FA_MAXG || (H % 2) || n_kv < 1) return -1;
+    const bool capped = logit_softcap != 0.0f;
+    if (capped && D != 128) return -1;
+    const float cscale = capped ? scale / logit_softcap : scale;
     uint16_t *q16 = (uint16_t *)((uint8_t *)ws + ((kcpp_fa_workspace_bytes(T, H, n_kv) + 255) & ~(int64_t)255));
     hipLaunchKernelGGL(k_q_to_f16, dim3(T, H), dim3(128), 0, s, (const char *)q, q_nb1, q_nb2, T, H, D, q16);
     KCPP_CHECK(hipGetLastError());
@@ -972,8 +1027,13 @@ int kcpp_flash_attn_ext(const float *q, int64_t q_nb1, int64_t q_nb2, const uint
         const dim3 grid(nch, HKV, T);
 #define KCPP_FA_CASE(GG)                                                                                          \
     case GG:                                                                                                      \
-        hipLaunchKernelGGL((k_fa_decode<128, GG>), grid, dim3(256), 0, s, q16, kc, vc, po, pml, T, H, HKV, n_kv,   \
-                           nullptr, nch, scale, mask, mask_ld, (int64_t)HKV * 128, (int64_t)128);                 \
+        if (capped)                                                                                               \
+            hipLaunchKernelGGL((k_fa_decode<128, GG, true>), grid, dim3(256), 0, s, q16, kc, vc, po, pml, T, H, HKV, \
+                               n_kv, nullptr, nch, cscale, mask, mask_ld, (int64_t)HKV * 128, (int64_t)128,       \
+                               logit_softcap);                                                                    \
+        else                                                                                                      \
+            hipLaunchKernelGGL((k_fa_decode<128, GG>), grid, dim3(256), 0, s, q16, kc, vc, po, pml, T, H, HKV,    \
+                               n_kv, nullptr, nch, scale, mask, mask_ld, (int64_t)HKV * 128, (int64_t)128);       \
         break;
         switch (H / HKV) {
             KCPP_FA_CASE(1)
@@ -990,12 +1050,21 @@ int kcpp_flash_attn_ext(const float *q, int64_t q_nb1, int64_t q_nb2, const uint
         KCPP_CHECK(hipGetLastError());
         hipLaunchKernelGGL(k_fa_combine<false>, dim3(H / 2, T), dim3(1024), 0, s, po, pml, out, (uint8_t *)nullptr, T, H,
                            D, n_kv, nullptr, nch, 1);
+    } else if (capped) {
+        hipLaunchKernelGGL((k_fa_prefill<128, true>), dim3((T + FP_BQ - 1) / FP_BQ, H), dim3(256), 0, s, q16, kc, vc, out,
+                           T, H, HKV, 0, cscale, mask, mask_ld, n_kv, (const int32_t *)nullptr, logit_softcap);
     } else {
         hipLaunchKernelGGL(k_fa_prefill<128>, dim3((T + FP_BQ - 1) / FP_BQ, H), dim3(256), 0, s, q16, kc, vc, out, T, H,
                            HKV, 0, scale, mask, mask_ld, n_kv, (const int32_t *)nullptr);
     }
     KCPP_CHECK(hipGetLastError());
     return 0;
+}
+int kcpp_flash_attn_ext(const float *q, int64_t q_nb1, int64_t q_nb2, const uint16_t *kc, const uint16_t *vc,
+                        const uint16_t *mask, int64_t mask_ld, float *out, void *ws, int T, int H, int HKV, int D,
+                        int n_kv, float scale, void *stream) {
+    return kcpp_flash_attn_ext_sc(q, q_nb1, q_nb2, kc, vc, mask, mask_ld, out, ws, T, H, HKV, D, n_kv, scale, stream,
+                                  0.0f);
 }
 
 }  // extern "C"

@@ -46,10 +46,12 @@ __device__ __forceinline__ void set_q_f32(State<G> &st, int g, const float4 a, c
 }
 
 // one 16-key group (keys base + 4 i + kq, i < 4; keys >= p1 masked), sc2 = scale * log2(e).  madd (optional): the
-// row's additive mask times log2(e), -inf = key skipped (its V never enters, as the CPU skips it)
-template <int G>
+// row's additive mask times log2(e), -inf = key skipped (its V never enters, as the CPU skips it).  CAP (the graph
+// form's logit soft-cap, ggml.c:15804-15810): sc2 = scale / cap and the score is cap2 * tanhf(dot * sc2) with
+// cap2 = cap * log2(e), then the mask
+template <int G, bool CAP = false>
 __device__ __forceinline__ void consume(State<G> &st, int base, int p1, int kq, float sc2, const uint4 *kk, const uint4 *vv,
-                                        const float *madd = nullptr) {
+                                        const float *madd = nullptr, float cap2 = 0.0f) {
     float s[G][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -83,7 +85,10 @@ __device__ __forceinline__ void consume(State<G> &st, int base, int p1, int kq, 
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             s[g][i] += dpp_f<0x140>(s[g][i]);
-            if (madd) {
+            if constexpr (CAP) {
+                const bool ok = base + 4 * i + kq < p1 && madd[i] != -INFINITY;
+                s[g][i] = ok ? __fadd_rn(cap2 * tanhf(s[g][i] * sc2), madd[i]) : -INFINITY;
+            } else if (madd) {
                 const bool ok = base + 4 * i + kq < p1 && madd[i] != -INFINITY;
                 s[g][i] = ok ? __fadd_rn(s[g][i] * sc2, madd[i]) : -INFINITY;
             } else {

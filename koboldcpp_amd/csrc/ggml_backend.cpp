@@ -17,9 +17,10 @@
 //   MUL_MAT_ID   quantized experts: expert-indexed mat-vecs reading the ids on the device (few rows), else the ids
 //                on the host and the gathered columns of all experts in one grouped GEMM (Q4_K / Q5_K / Q6_K) or
 //                one mat-vec / GEMM per expert (mul_mat_id below)
-//   FLASH_ATTN_EXT  kcpp_flash_attn_ext (graph-form Q view, F16 K/V cache views, F16 mask; head dim 64 / 128) or
-//                kcpp_flash_attn_ext_q (Q8_0 / Q4_0 K/V views: --quantkv)
-//   RMS_NORM, ROPE (NORM / NEOX, YaRN), SOFT_MAX, ADD/SUB/MUL/DIV (broadcast), SCALE, UNARY (SILU/NEG/RELU),
+//   FLASH_ATTN_EXT  kcpp_flash_attn_ext_sc (graph-form Q view, F16 K/V cache views, F16 mask; head dim 64 / 128 / 256,
+//                the logit soft-cap at 128 / 256: Gemma-2) or kcpp_flash_attn_ext_q (Q8_0 / Q4_0 K/V views: --quantkv,
+//                head dim 64 / 128, no soft-cap)
+//   RMS_NORM, ROPE (NORM / NEOX, YaRN), SOFT_MAX, ADD/SUB/MUL/DIV (broadcast), SCALE, UNARY (SILU/NEG/RELU/GELU/TANH),
 //   CPY/CONT/DUP (F32 <-> F16; F32 -> Q8_0 / Q4_0 cache stores), ARGSORT, SUM_ROWS: the general-layout kernels of
 //   ggml_ops.hip / attn_kvq.hip
 //   NONE/RESHAPE/VIEW/PERMUTE/TRANSPOSE: nothing (views)
@@ -594,8 +595,8 @@ bool supports(const kggml_tensor *op) {
         return f32(op) && f32(op->src[0]);
     case KGGML_OP_UNARY: {
         const int u = op->op_params[0];
-        return (u == KGGML_UNARY_OP_SILU || u == KGGML_UNARY_OP_NEG || u == KGGML_UNARY_OP_RELU) && f32(op) &&
-               f32(op->src[0]);
+        return (u == KGGML_UNARY_OP_SILU || u == KGGML_UNARY_OP_NEG || u == KGGML_UNARY_OP_RELU ||
+                u == KGGML_UNARY_OP_GELU || u == KGGML_UNARY_OP_TANH) && f32(op) && f32(op->src[0]);
     }
     case KGGML_OP_CPY: case KGGML_OP_CONT: case KGGML_OP_DUP: {
         const int s = op->src[0]->type, d = op->op == KGGML_OP_CPY ? op->src[1]->type : op->type;
@@ -640,18 +641,21 @@ bool supports(const kggml_tensor *op) {
                b->ne[3] == 1 && ids->ne[1] == b->ne[2] && op->ne[1] == ids->ne[0] && op->ne[2] == ids->ne[1];
     }
     case KGGML_OP_FLASH_ATTN_EXT: {
-        // ggml_cuda_flash_attn_ext (fattn.cu:210-218, 298-345): head dim 64 or 128; K / V both F16 cache views
-        // [n_kv][HKV][D], or both quantized Q8_0 / Q4_0 (--quantkv) views of ggml blocks at any block-aligned strides
+        // ggml_cuda_flash_attn_ext (fattn.cu:210-218, 298-345): head dim 64, 128 or 256; K / V both F16 cache views
+        // [n_kv][HKV][D], or (D 64 / 128) both quantized Q8_0 / Q4_0 (--quantkv) views of ggml blocks at any
+        // block-aligned strides.  The logit soft-cap (op_params[2], Gemma-2): F16 views at D 128 / 256 only.  No ALiBi.
         const kggml_tensor *q = op->src[0], *k = op->src[1], *v = op->src[2], *m = op->src[3];
-        if (!f32(op) || !f32(q) || op_f(op, 1) != 0.0f || op_f(op, 2) != 0.0f || q->ne[3] != 1) return false;
+        if (!f32(op) || !f32(q) || op_f(op, 1) != 0.0f || q->ne[3] != 1) return false;
         const int64_t D = q->ne[0], HKV = k->ne[2];
-        if ((D != 64 && D != 128) || k->ne[0] != D || v->ne[0] != D) return false;
+        const bool capped = op_f(op, 2) != 0.0f;
+        if ((D != 64 && D != 128 && D != 256) || k->ne[0] != D || v->ne[0] != D || (capped && D == 64)) return false;
         if (v->ne[1] != k->ne[1] || v->ne[2] != HKV || q->ne[2] % HKV || q->nb[0] != 4 || !is_contiguous(op) ||
             (m && !(m->type == KGGML_TYPE_F16 && m->nb[0] == 2)))
             return false;
         const bool kq = k->type == KGGML_TYPE_Q8_0 || k->type == KGGML_TYPE_Q4_0;
         const bool vq = v->type == KGGML_TYPE_Q8_0 || v->type == KGGML_TYPE_Q4_0;
         if (kq && vq) {
+            if (D == 256 || capped) return false;
             const size_t kb = kTraits[k->type].size, vb = kTraits[v->type].size;
             return k->nb[2] % kb == 0 && k->nb[1] % kb == 0 && v->nb[2] % vb == 0 && v->nb[1] % vb == 0 && k->nb[1] % 2 == 0;
         }
@@ -868,7 +872,8 @@ bool compute_node(BackendCtx *bc, kggml_tensor *n) {
     }
     case KGGML_OP_UNARY: {
         const int u = n->op_params[0];
-        const int k = u == KGGML_UNARY_OP_SILU ? KCPP_UN_SILU : u == KGGML_UNARY_OP_NEG ? KCPP_UN_NEG : KCPP_UN_RELU;
+        const int k = u == KGGML_UNARY_OP_SILU ? KCPP_UN_SILU : u == KGGML_UNARY_OP_NEG ? KCPP_UN_NEG
+                    : u == KGGML_UNARY_OP_GELU ? KCPP_UN_GELU : u == KGGML_UNARY_OP_TANH ? KCPP_UN_TANH : KCPP_UN_RELU;
         const kcpp_tdesc ta = td_of(a);
         return chk(kcpp_ggml_unary(k, a->data, &ta, n->data, &td, 0.0f, s), "unary");
     }
@@ -978,22 +983,24 @@ bool compute_node(BackendCtx *bc, kggml_tensor *n) {
                                              (int64_t)v->nb[2], mk, mld, (float *)n->data, T, H, HKV, D, n_kv, op_f(n, 0), s),
                        "flash_attn_ext(quantized K/V)");
         }
+        const float cap = op_f(n, 2);       // the logit soft-cap (0: none; D 128 / 256, supports())
         if (bc->fa_exact)
-            return chk(kcpp_flash_attn_ext_exact((const float *)q->data, (int64_t)q->nb[1], (int64_t)q->nb[2],
-                                                 (const uint16_t *)k->data, (const uint16_t *)v->data, mk, mld,
-                                                 (float *)n->data, T, H, HKV, D, n_kv, op_f(n, 0), s),
+            return chk(kcpp_flash_attn_ext_exact_sc((const float *)q->data, (int64_t)q->nb[1], (int64_t)q->nb[2],
+                                                    (const uint16_t *)k->data, (const uint16_t *)v->data, mk, mld,
+                                                    (float *)n->data, T, H, HKV, D, n_kv, op_f(n, 0), s, cap),
                        "flash_attn_ext(exact)");
         void *ws = bc->fa.get((size_t)kcpp_fa_ext_workspace_bytes(T, H, n_kv, D));
         if (!ws) return set_err("flash_attn_ext: workspace allocation failed");
         if (T == 1 && !bc->no_fused_mv) {   // one query: the production split kernel under the graph's mask, q rounded in it
-            const int rc = kcpp_flash_attn_ext_dec((const float *)q->data, (int64_t)q->nb[2], (const uint16_t *)k->data,
-                                                   (const uint16_t *)v->data, (int64_t)(k->nb[1] / 2), (int64_t)(k->nb[2] / 2),
-                                                   mk, (float *)n->data, ws, H, HKV, D, n_kv, op_f(n, 0), s);
+            const int rc = kcpp_flash_attn_ext_dec_sc((const float *)q->data, (int64_t)q->nb[2], (const uint16_t *)k->data,
+                                                      (const uint16_t *)v->data, (int64_t)(k->nb[1] / 2),
+                                                      (int64_t)(k->nb[2] / 2), mk, (float *)n->data, ws, H, HKV, D, n_kv,
+                                                      op_f(n, 0), s, cap);
             if (rc != -3) return chk(rc, "flash_attn_ext(decode)");
         }
-        return chk(kcpp_flash_attn_ext((const float *)q->data, (int64_t)q->nb[1], (int64_t)q->nb[2], (const uint16_t *)k->data,
-                                       (const uint16_t *)v->data, mk, mld, (float *)n->data, ws, T, H, HKV, D, n_kv,
-                                       op_f(n, 0), s),
+        return chk(kcpp_flash_attn_ext_sc((const float *)q->data, (int64_t)q->nb[1], (int64_t)q->nb[2],
+                                          (const uint16_t *)k->data, (const uint16_t *)v->data, mk, mld, (float *)n->data, ws,
+                                          T, H, HKV, D, n_kv, op_f(n, 0), s, cap),
                    "flash_attn_ext");
     }
     default:
@@ -1545,6 +1552,8 @@ kggml_backend_t ggml_backend_cuda_init(int device) {
     if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) { set_err("stream create failed"); return nullptr; }
     BackendCtx *c = new BackendCtx{device, KGGML_CUDA_NAME + std::to_string(device), s};
     c->fa_exact = getenv("KCPP_FA_EXACT") && atoi(getenv("KCPP_FA_EXACT")) != 0;
+    // the GELU node's f16 table (the reference's own, filled on the host with libm's tanhf) onto this device
+    if (kcpp_ggml_gelu_table_init() != 0) { (void)hipGetLastError(); set_err("GELU table upload failed"); }
     return new kggml_backend{&g_guid, kBackendIface, &g_devs[device], c};
 }
 bool ggml_backend_is_cuda(kggml_backend_t be) {

@@ -17,6 +17,11 @@
 #include "kcpp_common.h"
 #include "kcpp_internal.h"
 
+#include <cmath>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
 struct TD {
     int64_t ne[4];
     int64_t nb[4];
@@ -64,8 +69,13 @@ __global__ void k_bin(const char *__restrict__ a, TD ta, const char *__restrict_
 }
 
 // ---------------------------------------------------------------- unary / scale
+// gelu: ggml_vec_gelu_f32 with GGML_GELU_FP16 (ggml.c:2564-2578) -- 0 at x <= -10, x at x >= 10, else the f16 table
+// entry of f16(x).  The table (tab, 65536 f16 codes) is the reference's own (ggml_init, ggml.c:3820-3828), filled on
+// the host with libm's tanhf by gelu_table() below, so the result is the CPU backend's bit for bit.
+// tanh: ggml_vec_tanh_f32 (tanhf per element)
 template <int OP>
-__global__ void k_unary(const char *__restrict__ a, TD ta, char *__restrict__ d, TD td, float param, int64_t nrows) {
+__global__ void k_unary(const char *__restrict__ a, TD ta, char *__restrict__ d, TD td, float param, int64_t nrows,
+                        const uint16_t *__restrict__ tab = nullptr) {
     for (int64_t r = blockIdx.y; r < nrows; r += gridDim.y) {
         int64_t i1, i2, i3;
         row3(r, td.ne, i1, i2, i3);
@@ -77,6 +87,8 @@ __global__ void k_unary(const char *__restrict__ a, TD ta, char *__restrict__ d,
             if constexpr (OP == KCPP_UN_SILU) v = x / (1.0f + expf(-x));
             else if constexpr (OP == KCPP_UN_SCALE) v = __fmul_rn(x, param);
             else if constexpr (OP == KCPP_UN_NEG) v = -x;
+            else if constexpr (OP == KCPP_UN_GELU) v = x <= -10.0f ? 0.0f : (x >= 10.0f ? x : h2f(tab[f2h(x)]));
+            else if constexpr (OP == KCPP_UN_TANH) v = tanhf(x);
             else v = x > 0.0f ? x : 0.0f;                  // relu
             *(float *)(dr + i0 * td.nb[0]) = v;
         }
@@ -460,10 +472,83 @@ int kcpp_ggml_binary(int op, const void *a, const kcpp_tdesc *ta, const void *b,
     return 0;
 }
 
+// the reference's GELU table on the current device: table[i] = f16(ggml_gelu_f32(f32(f16 code i))) (ggml.c:2553-2555,
+// 3820-3825), computed once on the host -- the same libm tanhf the CPU backend calls -- and uploaded once per device
+// (128 KiB).  The expression is the reference's, operation for operation (this file is built without contraction, as
+// the reference's ISO-C build is).
+static float host_h2f(uint16_t h) {            // f16 code -> f32, exact (the F16C conversion's value)
+    const uint32_t s = (uint32_t)(h & 0x8000) << 16, e = (h >> 10) & 31, m = h & 0x3FF;
+    uint32_t x;
+    if (e == 0) {
+        const float f = (float)m * 5.9604644775390625e-8f;      // subnormal: m * 2^-24
+        memcpy(&x, &f, 4);
+        x |= s;
+    } else if (e == 31) {
+        x = s | 0x7F800000u | (m << 13);
+    } else {
+        x = s | ((e + 112) << 23) | (m << 13);
+    }
+    float f;
+    memcpy(&f, &x, 4);
+    return f;
+}
+static uint16_t host_f2h(float f) {            // f32 -> f16 code, round to nearest even (as F16C's _cvtss_sh)
+    uint32_t x;
+    memcpy(&x, &f, 4);
+    const uint16_t s = (uint16_t)((x >> 16) & 0x8000);
+    x &= 0x7FFFFFFFu;
+    if (x > 0x7F800000u) return s | 0x7E00;
+    if (x >= 0x477FF000u) return s | 0x7C00;                    // 65520 and above round to infinity
+    if (x < 0x38800000u) {                                      // below 2^-14: a subnormal f16, by one rounded addition
+        float a;
+        memcpy(&a, &x, 4);
+        a += 0.5f;
+        uint32_t y;
+        memcpy(&y, &a, 4);
+        return s | (uint16_t)(y - 0x3F000000u);
+    }
+    const uint32_t odd = (x >> 13) & 1;
+    x += 0xC8000FFFu;                                           // exponent bias 127 -> 15, plus 0xFFF
+    x += odd;
+    return s | (uint16_t)(x >> 13);
+}
+static const uint16_t *gelu_table() {
+    static std::mutex mu;
+    static std::vector<uint16_t> host;
+    static uint16_t *dev[64] = {nullptr};
+    int id = 0;
+    if (hipGetDevice(&id) != hipSuccess || id < 0 || id >= 64) return nullptr;
+    std::lock_guard<std::mutex> lk(mu);
+    if (dev[id]) return dev[id];
+    if (host.empty()) {
+        host.resize(1 << 16);
+        const float GELU_COEF_A = 0.044715f, SQRT_2_OVER_PI = 0.79788456080286535587989211986876f;
+        for (uint32_t i = 0; i < (1u << 16); ++i) {
+            const float x = host_h2f((uint16_t)i);
+            host[i] = host_f2h(0.5f * x * (1.0f + tanhf(SQRT_2_OVER_PI * x * (1.0f + GELU_COEF_A * x * x))));
+        }
+    }
+    uint16_t *p = nullptr;
+    if (hipMalloc((void **)&p, host.size() * 2) != hipSuccess) return nullptr;
+    if (hipMemcpy(p, host.data(), host.size() * 2, hipMemcpyHostToDevice) != hipSuccess) { hipFree(p); return nullptr; }
+    dev[id] = p;
+    return p;
+}
+
+int kcpp_ggml_gelu_table_init(void) { return gelu_table() ? 0 : -1; }
+
 int kcpp_ggml_unary(int op, const void *a, const kcpp_tdesc *ta, void *d, const kcpp_tdesc *td, float param,
                     void *stream) {
     const int64_t nr = nrows_of(td);
     if (nr == 0 || td->ne[0] == 0) return 0;
+    if (op == KCPP_UN_GELU) {
+        const uint16_t *tab = gelu_table();      // (already there when the backend made it at initialisation)
+        if (!tab) return -1;
+        hipLaunchKernelGGL(k_unary<KCPP_UN_GELU>, row_grid(td->ne[0], nr), dim3(256), 0, (hipStream_t)stream,
+                           (const char *)a, td_of(ta), (char *)d, td_of(td), param, nr, tab);
+        KCPP_CHECK(hipGetLastError());
+        return 0;
+    }
     const dim3 g = row_grid(td->ne[0], nr);
     hipStream_t s = (hipStream_t)stream;
 #define KU(OP) hipLaunchKernelGGL(k_unary<OP>, g, dim3(256), 0, s, (const char *)a, td_of(ta), (char *)d, td_of(td), param, nr)
@@ -472,6 +557,7 @@ int kcpp_ggml_unary(int op, const void *a, const kcpp_tdesc *ta, void *d, const 
     case KCPP_UN_SCALE: KU(KCPP_UN_SCALE); break;
     case KCPP_UN_NEG: KU(KCPP_UN_NEG); break;
     case KCPP_UN_RELU: KU(KCPP_UN_RELU); break;
+    case KCPP_UN_TANH: KU(KCPP_UN_TANH); break;
     default: return -2;
     }
 #undef KU

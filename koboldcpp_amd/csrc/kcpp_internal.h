@@ -209,3 +209,13 @@ int kcpp_model_step_linked(kcpp_model *m, int n_past);
 extern "C" int kcpp_flash_attn_ext_dec(const float *q, int64_t q_nb2, const uint16_t *kc, const uint16_t *vc, int64_t k_ld,
                                        int64_t k_hs, const uint16_t *mask, float *out, void *ws, int H, int HKV, int D,
                                        int n_kv, float scale, void *stream);
+// head dim 256 in the graph form (attn_d256.hip): the split decode kernel + combine for up to 16 queries (q_nb1 /
+// q_nb2: byte strides between queries / heads, key j of kv head h at kc + j k_ld + h k_hs elements, mask rows mask_ld
+// elements apart or null), the MFMA tile kernel for any T, and the decode pair's workspace.  -3: shape not covered
+extern "C" int64_t kcpp_fa256_ws_bytes(int T, int H);
+extern "C" int kcpp_fa256_dec(const float *q, int64_t q_nb1, int64_t q_nb2, const uint16_t *kc, const uint16_t *vc,
+                              int64_t k_ld, int64_t k_hs, const uint16_t *mask, int64_t mask_ld, float *out, void *ws, int T,
+                              int H, int HKV, int n_kv, float scale, float logit_softcap, void *stream);
+extern "C" int kcpp_fa256_prefill(const float *q, int64_t q_nb1, int64_t q_nb2, const uint16_t *kc, const uint16_t *vc,
+                                  const uint16_t *mask, int64_t mask_ld, float *out, int T, int H, int HKV, int n_kv,
+                                  float scale, float logit_softcap, void *stream);

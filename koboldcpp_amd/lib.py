@@ -106,6 +106,9 @@ _SIGS = {
     "kcpp_ggml_get_rows": [I, P, P, P, P, P, P, P],
     "kcpp_ggml_mul_mat_f": [I, P, P, P, P, P, P, P],
     "kcpp_flash_attn_ext": [P, I64, I64, P, P, P, I64, P, P, I, I, I, I, I, Fl, P],
+    "kcpp_flash_attn_ext_sc": [P, I64, I64, P, P, P, I64, P, P, I, I, I, I, I, Fl, P, Fl],
+    "kcpp_flash_attn_ext_dec_sc": [P, I64, P, P, I64, I64, P, P, P, I, I, I, I, Fl, P, Fl],
+    "kcpp_ggml_gelu_table_init": [],
     "kcpp_model_create": [P, P, I, I, I, I, I, I],
     "kcpp_model_synth_weights": [P, U64],
     "kcpp_model_set_tensor": [P, I, P, I64],
@@ -143,6 +146,7 @@ _SIGS = {
     "kcpp_gemm_grouped_ws_bytes": [I, I64, I64, I],
     "kcpp_flash_attn_exact": [P, P, P, P, I, I, I, I, I, P, Fl, P],
     "kcpp_flash_attn_ext_exact": [P, I64, I64, P, P, P, I64, P, I, I, I, I, I, Fl, P],
+    "kcpp_flash_attn_ext_exact_sc": [P, I64, I64, P, P, P, I64, P, I, I, I, I, I, Fl, P, Fl],
     "kcpp_model_weight_bytes": [P],
     "kcpp_model_set_kv_types": [P, I, I],
     "kcpp_rope_qk_inplace": [P, I64, I, I, I, I, I, P, P, P],
