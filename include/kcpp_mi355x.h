@@ -185,8 +185,9 @@ int kcpp_rope_kv_ex(const float *qkv, int64_t ldqkv, float *q_out, uint16_t *q16
 int kcpp_kv_shift_rows_ex(const uint16_t *kc, const uint16_t *vc, uint16_t *ks, uint16_t *vs, int64_t rows, int D,
                           const float *cs, int mode, void *stream);
 /* flash attention over the f16 cache (ggml_cuda_flash_attn_ext, fattn.cu:298-345) */
-/* force_path: 0 auto, 1 decode (T = 1: k_fa_dec4 splits + k_fa_comb4), 2 FMA-tiled prefill, 3 MFMA prefill
- * (D = 128, H = 4 HKV), 6 decode through the 64-key chunked kernel even at T = 1 */
+/* force_path: 0 auto, 1 decode (T = 1: k_fa_dec5 splits + k_fa_comb4), 2 FMA-tiled prefill, 3 MFMA prefill
+ * (D = 128, H = G HKV, G = 1..8), 6 decode through the 64-key chunked kernel even at T = 1, 7 the one-launch short
+ * form (T = 1, out only).  kcpp_fa_decode_plan says what a call runs. */
 int64_t kcpp_fa_workspace_bytes(int T, int H, int n_kv_max);
 int kcpp_flash_attn(const uint16_t *q16, const uint16_t *kc, const uint16_t *vc, float *out, void *qout, void *ws,
                     int T, int H, int HKV, int D, int n_past, const int32_t *n_past_dev, int n_kv_max, float scale,
@@ -227,8 +228,9 @@ int kcpp_flash_attn_q(int tk, int tv, const float *q, int64_t ldq, const void *k
                       int H, int HKV, int D, int64_t n_ctx, int n_past, const int32_t *n_past_dev, float scale,
                       void *stream);
 /* single-token decode attention with explicit cache strides in elements (key p of kv head hk at
- * kc + p*kv_ld + hk*kv_hs); variant 0: 64-key chunks + combine, 3: the production k_fa_dec4 splits +
- * k_fa_comb4 (A/B measurement entry, tools/fa_dec_bench.py) */
+ * kc + p*kv_ld + hk*kv_hs); variant 0: 64-key chunks + combine, 3: the legacy k_fa_dec4 splits + k_fa_comb4,
+ * 5: the production k_fa_dec5 splits + k_fa_comb4 (n_kv_max = the views' row count), 8: the one-launch short form,
+ * 6 / 7: tool forms of k_fa_dec5 (A/B measurement entry, tools/fa_dec_bench.py) */
 int kcpp_fa_decode_ex(const uint16_t *q16, const uint16_t *kc, const uint16_t *vc, int64_t kv_ld, int64_t kv_hs,
                       float *out, void *qout, void *ws, int H, int HKV, int n_past, const int32_t *n_past_dev,
                       int n_kv_max, float scale, int variant, void *stream);
@@ -240,7 +242,7 @@ void kcpp_fa_set_stamps(void *p);
 int kcpp_flash_attn_prefill_mfma(const uint16_t *q16, const uint16_t *kc, const uint16_t *vc, float *out, int T, int H,
                                  int HKV, int D, int n_past, float scale, void *stream);
 /* the same with, for T <= 64 and ws (kcpp_fa_workspace_bytes, zero before first use), the keys split over ~512
- * workgroups merged in-launch by the last split; out (f32 [T][H D], may be NULL) and/or qta (the KT_Q8_0_TA
+ * workgroups and merged by the next launch (k_fa_split_merge); out (f32 [T][H D], may be NULL) and/or qta (the KT_Q8_0_TA
  * activation of attn_output for KT_Q8_0_T weights, replacing kcpp_quantize_act; may be NULL).  -3 = not covered. */
 int kcpp_flash_attn_prefill_mfma_ex(const uint16_t *q16, const uint16_t *kc, const uint16_t *vc, float *out, void *qta,
                                     void *ws, int T, int H, int HKV, int D, int n_past, float scale, void *stream);
@@ -253,14 +255,28 @@ int64_t kcpp_fa_split_ws_bytes(int H);
  * KCPP_FA_PREFILL_MFMA=0 (environment, read once) sends every ratio but 4 to the FMA tiles.  -3: D != 128, H % HKV,
  * H / HKV > 8. */
 int kcpp_fa_prefill_plan(int T, int H, int HKV, int D, int n_past, int have_ws, int32_t out[8]);
+/* Launch plan of the decode attention and of the ggml-op forms (host only, no GPU; the rules are the comment block on
+ * fa_decode_plan in csrc/fa_plan.h).  form: 0 kcpp_flash_attn (and kcpp_flash_attn_dec_ta), 1 kcpp_fa_decode_ex, 2
+ * kcpp_flash_attn_ext_dec_sc, 3 kcpp_flash_attn_ext_sc (D = 256 is not planned here).  nkv: the key bound (forms 0, 1:
+ * n_kv_max when n_past_dev is given, else n_past + T; forms 2, 3: n_kv); n_rows: rows the K/V views hold, 0 = unknown;
+ * qkind: the quantized output, 0 none, 1 Q8_K, 2 KT_Q8_0_TA; sel: the force_path (form 0) or variant (form 1); flags:
+ * 1 = a logit soft-cap is set, 2 = no f32 out is given.  Returns the entry's error code, or 0 and out = {kernel: 0
+ * k_fa_decode + k_fa_combine, 1 k_fa_dec4 + k_fa_comb4, 2 k_fa_dec5 + k_fa_comb4, 3 k_fa_dec5<FINAL>, 4 k_fa_prefill
+ * tiles, 5 the MFMA prefill (kcpp_fa_prefill_plan has its geometry); ns; nch; waves; grid x, y, z; combine grid x, y;
+ * combine threads; combine quantizer (as qkind); then four byte counts from the start of the workspace as (low, high)
+ * 32-bit halves: part_o, part_ml, the end of what the launches touch, the f16 copy of Q (form 3; 0 = none)}.
+ * KCPP_FA_DEC=4 (environment, read once) plans kernel 1 in place of 2 at H / HKV in {1, 2, 4, 8} (form 0). */
+int kcpp_fa_decode_plan(int form, int T, int H, int HKV, int D, int nkv, int n_rows, int qkind, int sel, int flags,
+                        int32_t out[19]);
 /* single-token decode attention (the k_fa_dec5 + k_fa_comb4 pair) with the combine writing the KT_Q8_0_TA activation of
  * the token (qta) -- bit-identical to kcpp_quantize_act(KT_Q8_0_TA) of its f32 output; n_kv_max = the caches' row count
  * when n_past_dev is given (the graph-replayable form); -3 = not covered */
 int kcpp_flash_attn_dec_ta(const uint16_t *q16, const uint16_t *kc, const uint16_t *vc, float *out, void *qta, void *ws,
                            int H, int HKV, int D, int n_past, const int32_t *n_past_dev, int n_kv_max, float scale,
                            void *stream);
-/* MFMA prefill kernel generation: 2 (default; env KCPP_FA_MFMA_V) = next tile prefetched, V read through the
- * LDS transpose; 1 = the first version; 0 = the default.  Bit-identical outputs.  Returns the previous value. */
+/* MFMA prefill kernel generation: 4 (the default, k_fa_prefill_mfma3 on 8 waves, every GQA ratio) and, at H = 4 HKV
+ * alone, the A/B forms 1 (the first version), 2 (next tile prefetched, V read through the LDS transpose), 3 (four
+ * waves), 5 (HM); 0 = the default.  Returns the previous value. */
 int kcpp_fa_prefill_set_variant(int v);
 /* MoE router (llm_build_moe_ffn, src/llama.cpp:9435-9460): logits = W_router . x (W F16 -> x rounded
  * to f16 like the CPU vec_dot_f16, or F32), softmax, top-k (argsort descending), weights normalized to

@@ -23,6 +23,7 @@
 //       tile of 64 such keys is skipped.
 #include "kcpp_common.h"
 #include "kcpp_internal.h"
+#include "attn_common.h" // fa_for_g; fa_plan.h fa_splits
 #include "gemv_units.h"
 
 #include <algorithm>
@@ -384,14 +385,6 @@ __global__ void __launch_bounds__(256) k_fa256_mfma(const char *__restrict__ q, 
         *(float4 *)(op + 16 * db) = make_float4(o[db][0] * inv, o[db][1] * inv, o[db][2] * inv, o[db][3] * inv);
 }
 
-// one workgroup per CU over the splits x kv heads of one query (fa4_splits of attn.hip): independent of n_kv, so the
-// key partition -- and the result, bit for bit -- depends on the keys alone
-static int fa256_splits(int HKV) {
-    int ns = 4;
-    while (ns < FD_MAXS && 2 * ns * HKV <= 256) ns *= 2;
-    return ns;
-}
-
 extern "C" {
 
 // partial O [T][H][NS][256] + (m, l) [T][H][NS] behind the workspace header, for the up to 16 queries of the decode pair
@@ -407,26 +400,24 @@ int kcpp_fa256_dec(const float *q, int64_t q_nb1, int64_t q_nb2, const uint16_t 
     // 16-B loads: q rows, K / V rows
     if (q_nb1 % 16 || q_nb2 % 16 || ((uintptr_t)q & 15) || k_ld % 8 || k_hs % 8 || ((uintptr_t)kc & 15) || ((uintptr_t)vc & 15))
         return -3;
-    const int G = H / HKV, NS = fa256_splits(HKV);
-    if (!(G == 1 || G == 2 || G == 4 || G == 8)) return -3;
+    // one workgroup per CU over the splits x kv heads of one query (fa_plan.h fa_splits): independent of n_kv, so the
+    // key partition -- and the result, bit for bit -- depends on the keys alone
+    const int G = H / HKV, NS = fa_splits(HKV, FD_MAXS);
     hipStream_t s = (hipStream_t)stream;
     float *po = (float *)((uint8_t *)ws + KCPP_FA_WS_HEADER);
     float2 *pml = (float2 *)(po + (int64_t)T * H * NS * FD_D);
     const bool capped = logit_softcap != 0.0f;
     const float cscale = capped ? scale / logit_softcap : scale;
-#define KCPP_FD(GG)                                                                                                    \
-    case GG:                                                                                                           \
-        if (capped)                                                                                                    \
-            hipLaunchKernelGGL((k_fa256_dec<GG, true>), dim3(NS, HKV, T), dim3(256), 0, s, q, q_nb1 / 4, q_nb2 / 4, kc, vc, \
-                               k_ld, k_hs, mask, mask_ld, po, pml, H, n_kv, NS, cscale, logit_softcap);               \
-        else                                                                                                           \
-            hipLaunchKernelGGL((k_fa256_dec<GG, false>), dim3(NS, HKV, T), dim3(256), 0, s, q, q_nb1 / 4, q_nb2 / 4, kc, vc, \
-                               k_ld, k_hs, mask, mask_ld, po, pml, H, n_kv, NS, cscale, 0.0f);                        \
-        break;
-    switch (G) {
-        KCPP_FD(1) KCPP_FD(2) KCPP_FD(4) KCPP_FD(8)
-    }
-#undef KCPP_FD
+    const int rc = fa_for_g<1, 2, 4, 8>(G, [&](auto g) {
+        constexpr int GG = decltype(g)::value;
+        if (capped)
+            hipLaunchKernelGGL((k_fa256_dec<GG, true>), dim3(NS, HKV, T), dim3(256), 0, s, q, q_nb1 / 4, q_nb2 / 4, kc, vc,
+                               k_ld, k_hs, mask, mask_ld, po, pml, H, n_kv, NS, cscale, logit_softcap);
+        else
+            hipLaunchKernelGGL((k_fa256_dec<GG, false>), dim3(NS, HKV, T), dim3(256), 0, s, q, q_nb1 / 4, q_nb2 / 4, kc, vc,
+                               k_ld, k_hs, mask, mask_ld, po, pml, H, n_kv, NS, cscale, 0.0f);
+    });
+    if (rc) return rc;
     KCPP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(k_fa256_comb, dim3(H, T), dim3(256), 0, s, po, pml, out, H, NS);
     KCPP_CHECK(hipGetLastError());

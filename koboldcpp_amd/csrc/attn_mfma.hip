@@ -20,6 +20,7 @@
 #include "kcpp_common.h"
 #include "kcpp_internal.h"
 #include "fa_plan.h"     // FM_Q, FM_K, the split constants, the launch plan
+#include "attn_common.h" // fa_for_g
 
 #include <algorithm>
 #include <cstdlib>
@@ -767,20 +768,11 @@ static int fa_mfma3_run(const FaPrefillPlan &p, const uint16_t *q16, const uint1
 
 static int fa_mfma3_run_g(const FaPrefillPlan &p, const uint16_t *q16, const uint16_t *kc, const uint16_t *vc, float *out,
                           uint8_t *qta, void *ws, int T, int H, int HKV, int n_past, float scale, hipStream_t s) {
-    switch (H / HKV) {
-#define KCPP_FM_CASE(GG) \
-    case GG: return fa_mfma3_run<GG>(p, q16, kc, vc, out, qta, ws, T, H, HKV, n_past, scale, s);
-        KCPP_FM_CASE(1)
-        KCPP_FM_CASE(2)
-        KCPP_FM_CASE(3)
-        KCPP_FM_CASE(4)
-        KCPP_FM_CASE(5)
-        KCPP_FM_CASE(6)
-        KCPP_FM_CASE(7)
-        KCPP_FM_CASE(8)
-#undef KCPP_FM_CASE
-    }
-    return -3;
+    int rc = 0;
+    const int rg = fa_for_g<1, 2, 3, 4, 5, 6, 7, 8>(H / HKV, [&](auto g) {
+        rc = fa_mfma3_run<decltype(g)::value>(p, q16, kc, vc, out, qta, ws, T, H, HKV, n_past, scale, s);
+    });
+    return rg ? rg : rc;
 }
 
 // kcpp_fa_prefill_set_variant's numbers other than 4 (1, 2: the v1 / v2 kernels, 3: four waves, 5: HM) are A/B

@@ -2,9 +2,8 @@
 #pragma once
 #include <stdint.h>
 
-// bytes in front of the flash-attention workspace's partials (spare header words for in-launch hand-offs)
-#define KCPP_FA_WS_HEADER 2048
-// single-token decode attention: contexts up to this many keys would run the one-launch kernel (attn.hip fa_short_launch;
+#include "fa_plan.h"     // KCPP_FA_WS_HEADER, the attention launch plans
+// single-token decode attention: contexts up to this many keys would run the one-launch kernel (attn_dec.hip fa_short_launch;
 // off: one workgroup per kv head measured slower than the split pair at every size, 10.3 vs 7.8 us at 300 keys;
 // runtime.cpp picks the regime per step, KCPP_FA_SHORT overrides)
 #define KCPP_FA_SHORT_MAX 0

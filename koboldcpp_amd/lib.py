@@ -69,6 +69,7 @@ _SIGS = {
     "kcpp_flash_attn_prefill_mfma_ex": [P, P, P, P, P, P, I, I, I, I, I, Fl, P],
     "kcpp_fa_split_ws_bytes": [I],
     "kcpp_fa_prefill_plan": [I, I, I, I, I, I, P],
+    "kcpp_fa_decode_plan": [I, I, I, I, I, I, I, I, I, I, P],
     "kcpp_flash_attn_dec_ta": [P, P, P, P, P, P, I, I, I, I, P, I, Fl, P],
     "kcpp_fa_decode_ex": [P, P, P, I64, I64, P, P, P, I, I, I, P, I, Fl, I, P],
     "kcpp_fa_set_stamps": [P],
@@ -496,6 +497,28 @@ def fa_prefill_plan(T, H, HKV, D=128, n_past=0, have_ws=False):
     _chk(rc, "fa_prefill_plan")
     d = dict(zip(("kernel", "gh", "qb", "nb0", "nsp", "ch", "merge_grid", "part_bytes"), out))
     d["kernel"] = FA_PREFILL_KERNEL[d["kernel"]]
+    return d
+
+
+FA_DEC_KERNEL = ("chunk", "split4", "split5", "short", "tile", "mfma")
+FA_FORM = ("runtime", "ex", "graph1", "grapht")
+
+
+def fa_decode_plan(form, T, H, HKV, D=128, nkv=1, n_rows=0, qkind=0, sel=0, cap=False, have_out=True):
+    """what a decode / ggml-op attention entry launches (kcpp_fa_decode_plan; host only).  form: a FA_FORM name; sel: the
+    force_path or variant.  Returns the entry's error code (a negative int), or a dict of kernel (a FA_DEC_KERNEL name),
+    ns, nch, waves, grid, cgrid, cthreads, cquant and the workspace byte offsets part_o, part_ml, ws_bytes, q16"""
+    out = (ctypes.c_int32 * 19)()
+    rc = _L.kcpp_fa_decode_plan(FA_FORM.index(form), int(T), int(H), int(HKV), int(D), int(nkv), int(n_rows), int(qkind),
+                                int(sel), int(bool(cap)) | (0 if have_out else 2), out)
+    if rc:
+        return rc
+    v = list(out)
+    d = dict(zip(("kernel", "ns", "nch", "waves"), v[:4]), grid=tuple(v[4:7]), cgrid=tuple(v[7:9]), cthreads=v[9],
+             cquant=v[10])
+    for i, k in enumerate(("part_o", "part_ml", "ws_bytes", "q16")):
+        d[k] = (v[11 + 2 * i] & 0xFFFFFFFF) | (v[12 + 2 * i] << 32)
+    d["kernel"] = FA_DEC_KERNEL[d["kernel"]]
     return d
 
 

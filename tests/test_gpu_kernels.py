@@ -360,7 +360,7 @@ def test_fa_dec4_split_counts(env, H, HKV, variant):
 @pytest.mark.parametrize("path", [1, 6])
 @pytest.mark.parametrize("n_past", [63, 2047, 4095])
 def test_flash_attn_decode_long_ctx(env, n_past, path):
-    """decode (1: the production k_fa_dec4 splits + k_fa_comb4; 6: 64-key chunks + combine) at 4k context,
+    """decode (1: the production k_fa_dec5 splits + k_fa_comb4; 6: 64-key chunks + combine) at 4k context,
     graph-style device n_past, vs the f32-accumulation oracle; twice in a row with the same workspace."""
     torch, K = env
     H, HKV, D, n_ctx = 32, 8, 128, 4096
