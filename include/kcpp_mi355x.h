@@ -104,18 +104,19 @@ int kcpp_gemm_q80_segs(const void *const *W, const int64_t *N, int nseg, int64_t
 
 /* Fused single-token mat-vec (koboldcpp_amd/csrc/gemv_dec.hip): args points at a DecArgs struct
  * (koboldcpp_amd/csrc/kcpp_internal.h, size kcpp_gemv_dec_args_size()).  mode 0 plain(+res),
- * 1 silu-GLU, 2 RoPE + K/V-cache store; pro 0 act given, 1 rms_norm+quantize prologue, 2 quantize. */
+ * 1 silu-GLU, 2 RoPE + K/V-cache store; pro 0 act given, 1 rms_norm+quantize prologue, 2 quantize.
+ * Which kernel a call runs, with which instance and grid, and every refusal code is decided once, by the launch
+ * plan (koboldcpp_amd/csrc/gemv_plan.h, the rules block at its top); kcpp_gemv_dec_plan returns it. */
 int kcpp_gemv_dec(int type, const void *args, int mode, int pro, int rows_per_wave, void *stream);
 int64_t kcpp_gemv_dec_args_size(void);
-/* the coalesced-streaming Q4_K variant kcpp_gemv_dec dispatches to (koboldcpp_amd/csrc/gemv_stream.hip);
- * returns -3 when the type/shape/mode is not covered.  Exposed for the parity tests and tools. */
+/* the single kernel families' entries: the same plan restricted to one kernel, -3 when that kernel does not cover
+ * the call.  Exposed for the parity tests and tools.  kcpp_gemv_stream: the coalesced-streaming Q4_K kernel
+ * (gemv_stream.hip); kcpp_gemv_q4k: the VALU-lean unit-per-lane Q4_K kernel (gemv_q4k.hip); kcpp_gemv_rs: the
+ * row-major decode layouts KT_Q4_K_RS / KT_Q5_K_RS / KT_Q6_K_RS (gemv_rs.hip; kcpp_gemv_dec runs these types there).
+ * kcpp_rs_supported(type, K) says whether a [K x N] weight of Q4_K / Q5_K / Q6_K (or its RS id) can be held in the
+ * RS layout. */
 int kcpp_gemv_stream(int type, const void *args, int mode, int pro, void *stream);
-/* the VALU-lean unit-per-lane Q4_K variant (koboldcpp_amd/csrc/gemv_q4k.hip), tried first for Q4_K;
- * -3 when not covered */
 int kcpp_gemv_q4k(const void *args, int mode, int pro, void *stream);
-/* single-token mat-vec over the row-major decode layouts KT_Q4_K_RS / KT_Q6_K_RS (type ids 112 / 114,
- * koboldcpp_amd/csrc/gemv_rs.hip); kcpp_gemv_dec dispatches these types here.  kcpp_rs_supported(type, K)
- * says whether a [K x N] weight of Q4_K / Q6_K (or its RS id) can be held in the RS layout. */
 int kcpp_gemv_rs(int type, const void *args, int mode, int pro, void *stream);
 /* q|k|v decode projection (mode 2, rms_norm + Q8_K prologue) with segments 0, 1 (q, k) in KT_Q4_K_RS and segment 2
  * (v) in KT_Q6_K_RS -- the Q4_K_M "more bits" layers -- in one launch; -3 when the shape is not covered */
@@ -125,6 +126,20 @@ int kcpp_gemv_rs_qkv_mixed(const void *args, void *stream);
  * kcpp_gemv_dec calls); -3 when not covered */
 int kcpp_gemv_qkv_dual(const void *qargs, int qtype, const void *kvargs, void *stream);
 int kcpp_rs_supported(int type, int64_t K);
+/* What a fused mat-vec entry runs for a call (host only; gemv_plan.h GemvPlan).  entry: 0 kcpp_gemv_dec, 1 kcpp_gemv_rs,
+ * 2 kcpp_gemv_rs_aux, 3 kcpp_gemv_q4k, 4 kcpp_gemv_stream, 5 the unit-per-lane kernels alone; flags: what the DecArgs /
+ * AuxOut hold (GEMV_F_*).  Returns the entry's return code and fills out = {rc, kernel (0 RS, 1 RS aux, 2 Q4K,
+ * 3 stream, 4 unit), type, mode, pro, NI, IT, LPR, R, MC, PF, waves, XL, ROUTE, EX, block, nblk, lds_bytes}. */
+int kcpp_gemv_dec_plan(int entry, int type, int64_t K, int nseg, int64_t N0, int64_t N1, int64_t N2, int role0, int role1,
+                       int role2, int D, int mode, int pro, int rows_per_wave, int flags, int route_wt, int route_ne,
+                       int32_t out[18]);
+/* the same for kcpp_gemv_rs_qkv_mixed: out = {rc, NIA, NIB, MC, EX, block, nblk, lds_bytes} */
+int kcpp_gemv_qkv_mixed_plan(int64_t K, int64_t N0, int64_t N1, int64_t N2, int role0, int role1, int role2, int D,
+                             int flags, int32_t out[8]);
+/* and for kcpp_gemv_qkv_dual (q: nseg_a segments Na of qtype; k|v: nseg_b segments Nb of Q8_0):
+ * out = {rc, nblk, lds_bytes, q half nblk, lds_bytes, NI, k|v half nblk, lds_bytes, IT} */
+int kcpp_gemv_qkv_dual_plan(int qtype, int64_t Ka, int nseg_a, const int64_t *Na, int flags_a, int64_t Kb, int nseg_b,
+                            const int64_t *Nb, int flags_b, int32_t out[9]);
 
 /* rms_norm (ggml.c:12059) * w, optionally quantized to Q8_K in the same pass (q8k_out) */
 int kcpp_rms_norm(const float *x, int64_t ldx, const float *w, float *y, int64_t ldy, void *q8k_out, int64_t ne0,

@@ -148,77 +148,24 @@ __global__ void __launch_bounds__(256) k_gemv_dec(const DecArgs a) {
 #undef KB_ARGS
 }
 
-// grid and LDS of k_gemv_dec<TYPE, R, MODE, PRO, ...> for a (launch_dec_it's rule)
-template <int TYPE, int R, int PRO>
-static int64_t dec_grid(const DecArgs &a, size_t &lds) {
-    int64_t ntot = 0;
-    for (int i = 0; i < a.nseg; ++i) ntot += a.N[i];
-    const int max_blocks = a.K > 4096 ? 512 : 1024;
-    const int64_t groups = ntot / R;
-    const int vt = (TYPE == KT_Q4_0 || TYPE == KT_Q5_0 || TYPE == KT_Q8_0 || TYPE == KT_IQ4_NL) ? KT_Q8_0 : KT_Q8_K;
-    lds = PRO ? (size_t)act_bytes(vt, a.K, 1) + 16 : 0;
-    return std::min<int64_t>((groups + 3) / 4, max_blocks);
-}
+// The built instances (R, MODE, PRO, MC), each at IT 1 / 2 / 4 (PRO 2: 2 / 4 / 8): what the plan's GEMV_UNIT rules name
+// (gemv_plan.h), nothing else
+#define KCPP_UNIT_INSTANCES(X)                                                                                        \
+    X(2, 2, 1, 1) X(2, 2, 1, 2) X(2, 1, 1, 1) X(2, 1, 1, 2) X(1, 1, 1, 1) X(1, 1, 1, 2) X(4, 0, 0, 1) X(2, 0, 0, 1)    \
+    X(1, 0, 0, 1) X(2, 0, 1, 1) X(2, 0, 1, 2) X(1, 0, 1, 1) X(1, 0, 1, 2) X(1, 0, 2, 2) X(1, 0, 2, 4) X(1, 0, 2, 8)
 
-template <int TYPE, int R, int MODE, int PRO, int MC, int IT>
-static int launch_dec_it(const DecArgs &a, hipStream_t s) {
-    int64_t ntot = 0;
-    for (int i = 0; i < a.nseg; ++i) {
-        if (a.N[i] % R) return -5;
-        ntot += a.N[i];
-    }
-    if (PRO != 0 && a.K > 4096 * MC) return -6;
-    // 1024 workgroups for K = n_embd shapes (the output head prefers more), 512 for the K = n_ff
-    // quantize-prologue shape (ffn_down: 20.6 vs 26.8 us measured)
-    size_t lds = 0;
-    const int64_t nblk = dec_grid<TYPE, R, PRO>(a, lds);
-    hipLaunchKernelGGL((k_gemv_dec<TYPE, R, MODE, PRO, MC, IT>), dim3((unsigned)nblk), dim3(256), lds, s, a);
-    KCPP_CHECK(hipGetLastError());
-    return 0;
-}
-
-// IT = K-slices per lane: K/E/64 (Q4_K K=4096 -> 1, K=14336 -> 4; Q4_0/Q8_0 double).
-// The ffn_down prologue (PRO 2) covers K = n_ff: IT 2..8; everything else K = n_embd: IT 1..4.
-template <int TYPE, int R, int MODE, int PRO, int MC>
-static int launch_dec(const DecArgs &a, hipStream_t s) {
-    const int64_t upr = a.K / Unit<TYPE>::ELEMS;
-    const int64_t it = (upr + 63) / 64;
-    if constexpr (PRO == 2) {
-        if (it <= 2) return launch_dec_it<TYPE, R, MODE, PRO, MC, 2>(a, s);
-        if (it <= 4) return launch_dec_it<TYPE, R, MODE, PRO, MC, 4>(a, s);
-        if (it <= 8) return launch_dec_it<TYPE, R, MODE, PRO, MC, 8>(a, s);
-    } else {
-        if (it <= 1) return launch_dec_it<TYPE, R, MODE, PRO, MC, 1>(a, s);
-        if (it <= 2) return launch_dec_it<TYPE, R, MODE, PRO, MC, 2>(a, s);
-        if (it <= 4) return launch_dec_it<TYPE, R, MODE, PRO, MC, 4>(a, s);
-    }
-    return -8;
-}
-
-// only the (mode, prologue, rows, chunk) combinations the runtime uses are instantiated
 template <int TYPE>
-int dispatch_mode(const DecArgs &a, int mode, int pro, int rows_per_wave, hipStream_t s) {
-    const int64_t mc = (a.K + 4095) / 4096;
-    if (mode == 2) {
-        if (pro != 1) return -7;
-        return mc <= 1 ? launch_dec<TYPE, 2, 2, 1, 1>(a, s) : launch_dec<TYPE, 2, 2, 1, 2>(a, s);
+int gemv_unit_launch(const GemvPlan &p, const DecArgs &a, hipStream_t s) {
+    void (*k)(const DecArgs) = nullptr;
+#define KCPP_UNIT_PICK(R_, MODE_, PRO_, MC_)                                                                          \
+    if (p.R == R_ && p.mode == MODE_ && p.pro == PRO_ && p.MC == MC_) {                                               \
+        constexpr int I0 = PRO_ == 2 ? 2 : 1;                                                                         \
+        if (p.IT == I0) k = k_gemv_dec<TYPE, R_, MODE_, PRO_, MC_, I0>;                                               \
+        if (p.IT == 2 * I0) k = k_gemv_dec<TYPE, R_, MODE_, PRO_, MC_, 2 * I0>;                                       \
+        if (p.IT == 4 * I0) k = k_gemv_dec<TYPE, R_, MODE_, PRO_, MC_, 4 * I0>;                                       \
     }
-    if (mode == 1) {
-        if (pro != 1) return -7;
-        if (rows_per_wave >= 2) return mc <= 1 ? launch_dec<TYPE, 2, 1, 1, 1>(a, s) : launch_dec<TYPE, 2, 1, 1, 2>(a, s);
-        return mc <= 1 ? launch_dec<TYPE, 1, 1, 1, 1>(a, s) : launch_dec<TYPE, 1, 1, 1, 2>(a, s);
-    }
-    if (pro == 0) {
-        if (rows_per_wave >= 4) return launch_dec<TYPE, 4, 0, 0, 1>(a, s);
-        if (rows_per_wave >= 2) return launch_dec<TYPE, 2, 0, 0, 1>(a, s);
-        return launch_dec<TYPE, 1, 0, 0, 1>(a, s);
-    }
-    if (pro == 1) {
-        if (rows_per_wave >= 2) return mc <= 1 ? launch_dec<TYPE, 2, 0, 1, 1>(a, s) : launch_dec<TYPE, 2, 0, 1, 2>(a, s);
-        return mc <= 1 ? launch_dec<TYPE, 1, 0, 1, 1>(a, s) : launch_dec<TYPE, 1, 0, 1, 2>(a, s);
-    }
-    if (mc <= 2) return launch_dec<TYPE, 1, 0, 2, 2>(a, s);
-    if (mc <= 4) return launch_dec<TYPE, 1, 0, 2, 4>(a, s);
-    return launch_dec<TYPE, 1, 0, 2, 8>(a, s);
+    KCPP_UNIT_INSTANCES(KCPP_UNIT_PICK)
+#undef KCPP_UNIT_PICK
+    void *args[] = {(void *)&a};
+    return gemv_go(p.type == TYPE ? (const void *)k : nullptr, p.nblk, p.block, p.lds_bytes, args, s);
 }
-

@@ -200,43 +200,24 @@ __global__ void __launch_bounds__(256) k_gemv_q4k(const DecArgs a) {
     lean::store_group<R, MODE>(a, seg, row0, slot);
 }
 
-namespace {
-template <int IT, int R, int MODE, int PRO, int MC, int PF>
-int launch_q4k(const DecArgs &a, hipStream_t s) {
-    int64_t ntot = 0;
-    for (int i = 0; i < a.nseg; ++i) {
-        if (a.N[i] % R) return -5;
-        ntot += a.N[i];
-    }
-    const int64_t groups = ntot / R;
-    // measured (tools/stream_probe.py sweep): 512 workgroups (2 per CU) for every shape, 256 for gate|up with
-    // R = 2 -- fewer prologues (each workgroup re-derives the activation) and less queueing than 1024
-    const int max_blocks = MODE == 1 && R == 2 ? 256 : 512;
-    int64_t nblk = std::min<int64_t>((groups + 3) / 4, max_blocks);
-    nblk = std::max<int64_t>(nblk, (groups + 255) / 256);    // <= 64 groups per wave (result slots)
-    const int64_t abytes = a.K + a.K / 256 * 4 + a.K / 16 * 2;
-    hipLaunchKernelGGL((k_gemv_q4k<IT, R, MODE, PRO, MC, PF>), dim3((unsigned)nblk), dim3(256), (size_t)abytes + 16, s, a);
-    KCPP_CHECK(hipGetLastError());
-    return 0;
-}
-}  // namespace
+// The built instances (IT, R, MODE, PRO, MC, PF): the plan's GEMV_Q4K rules (gemv_plan.h) name these and no other
+#define KCPP_Q4K_INSTANCES(X) X(1, 2, 1, 1, 1, 1) X(1, 2, 2, 1, 1, 0) X(1, 1, 0, 0, 1, 0) X(1, 2, 0, 1, 1, 1) X(4, 1, 0, 2, 4, 0) X(4, 1, 0, 0, 4, 0)
 
-// -3 = not covered (caller falls back)
+int gemv_q4k_launch(const GemvPlan &p, const DecArgs &a, hipStream_t s) {
+    void (*k)(const DecArgs) = nullptr;
+#define KCPP_Q4K_PICK(IT_, R_, MODE_, PRO_, MC_, PF_)                                                                 \
+    if (p.IT == IT_ && p.R == R_ && p.mode == MODE_ && p.pro == PRO_ && p.MC == MC_ && p.PF == PF_)                   \
+        k = k_gemv_q4k<IT_, R_, MODE_, PRO_, MC_, PF_>;
+    KCPP_Q4K_INSTANCES(KCPP_Q4K_PICK)
+#undef KCPP_Q4K_PICK
+    void *args[] = {(void *)&a};
+    return gemv_go(p.kernel == GEMV_Q4K ? (const void *)k : nullptr, p.nblk, p.block, p.lds_bytes, args, s);
+}
+
+// the plan restricted to this kernel; -3 = not covered
 extern "C" int kcpp_gemv_q4k(const void *args, int mode, int pro, void *stream) {
     const DecArgs &a = *(const DecArgs *)args;
-    hipStream_t s = (hipStream_t)stream;
-    if (a.nseg < 1 || a.nseg > 3) return -3;
-    if (mode == 2 && dec_args_ex(a)) return -3;          // q|k|v bias / NeoX pairs: the RS kernels only
-    // gate|up: R = 2 with prefetch at 256 workgroups (17.5 us vs 21.1 us for gemv_dec_impl.h)
-    if (a.K == 4096) {
-        if (mode == 1 && pro == 1) return launch_q4k<1, 2, 1, 1, 1, 1>(a, s);
-        if (mode == 2 && pro == 1) return launch_q4k<1, 2, 2, 1, 1, 0>(a, s);
-        if (mode == 0 && pro == 0) return launch_q4k<1, 1, 0, 0, 1, 0>(a, s);
-        if (mode == 0 && pro == 1) return launch_q4k<1, 2, 0, 1, 1, 1>(a, s);
-        return -3;
-    }
-    // ffn_down (K = 14336): R = 1 without prefetch (tools/probe_down sweep: R 2 / prefetch variants no faster)
-    if (a.K == 14336 && mode == 0 && pro == 2) return launch_q4k<4, 1, 0, 2, 4, 0>(a, s);
-    if (a.K == 14336 && mode == 0 && pro == 0) return launch_q4k<4, 1, 0, 0, 4, 0>(a, s);
-    return -3;
+    GemvPlan p;
+    if (gemv_plan(gemv_shape_of(KT_Q4_K, a, mode, pro, 0), GEMV_ENTRY_Q4K, &p)) return p.rc;
+    return gemv_q4k_launch(p, a, (hipStream_t)stream);
 }

@@ -95,143 +95,92 @@ __global__ void __launch_bounds__(64 * NWV) k_gemv_rs_aux(const int kb_nblk, con
 #include "gemv_rs_body.inc"
 }
 
+#ifndef Q_PF
+#define Q_PF 0               // MODE 3 group prefetch and XL: the instance's compile-time probes (gemv_plan.h, mode 3)
+#endif
+#ifndef Q_XL
+#define Q_XL false
+#endif
+
 namespace {
-// the ggml plugin's AuxOut for the launches below (kcpp_gemv_rs_aux; null: the runtime's plain launches)
-thread_local const AuxOut *g_rs_aux = nullptr;
+// The built instances of one (TYPE, NI, MC) class, registers-resident activation: (R, MODE, PRO, PF, NWV, ROUTE, EX),
+// then the AUX kernel's (R, MODE, PRO, PF, NWV).  The plan (gemv_plan.h, GEMV_RS / GEMV_RS_AUX) chooses among them; the
+// prefetching forms of the PF 0 shapes and the reverse are built and never chosen.
+#define KCPP_RS_BY_PRO(X, PRO_)                                                                                       \
+    X(1, 1, PRO_, 1, 4, false, false) X(1, 1, PRO_, 0, 4, false, false) X(2, 2, PRO_, 0, 4, false, false)              \
+    X(2, 0, PRO_, 1, 4, false, false) X(2, 0, PRO_, 0, 4, false, false) X(1, 0, PRO_, 1, 4, false, false)              \
+    X(1, 0, PRO_, 0, 4, false, false)
+#define KCPP_RS_INSTANCES(X)                                                                                          \
+    KCPP_RS_BY_PRO(X, 0) KCPP_RS_BY_PRO(X, 1) KCPP_RS_BY_PRO(X, 2)                                                     \
+    X(1, 1, 1, 1, 8, false, false) X(1, 0, 2, 0, 8, false, false) X(2, 2, 1, 0, 4, false, true)
+#define KCPP_RS_AUX_INSTANCES(X) X(2, 0, 2, 0, 4) X(2, 0, 1, 0, 4) X(1, 0, 2, 0, 8) X(1, 1, 2, 1, 4) X(1, 1, 1, 1, 8)
+// long K (XL, NI a ceiling, 8 waves, no prefetch): (R, MODE, PRO)
+#define KCPP_RS_XL_INSTANCES(X) X(1, 0, 2) X(1, 0, 1) X(1, 0, 0) X(1, 1, 1) X(1, 1, 0) X(2, 2, 1)
 
-template <int TYPE, int NI, int R, int MODE, int PRO, int MC, int PF, int NWV = 4, bool XL = false, bool ROUTE = false,
-          bool AUX = false, bool EX = false>
-int launch_rs(const DecArgs &a, int max_blocks, hipStream_t s) {
-    int64_t ntot = 0;
-    for (int i = 0; i < a.nseg; ++i) {
-        if (a.N[i] % R) return -5;
-        ntot += a.N[i];
-    }
-    const int64_t groups = ntot / R;
-    constexpr int WPG = MODE == 3 ? NWV / 2 : NWV;
-    int64_t nblk = std::min<int64_t>((groups + WPG - 1) / WPG, max_blocks);
-    nblk = std::max<int64_t>(nblk, (groups + 64 * WPG - 1) / (64 * WPG));    // <= 64 groups per wave (result slots)
-    const int64_t abytes = a.K + a.K / 256 * 4 + a.K / 16 * 2;
-    const int64_t lbytes = MODE == 3 ? 2 * ((abytes + 15) & ~(int64_t)15) : abytes;
-    if constexpr (AUX) {
-        static_assert(!XL && !ROUTE, "AUX instances: plain single-token launches");
-        hipLaunchKernelGGL((k_gemv_rs_aux<TYPE, NI, R, MODE, PRO, MC, PF, NWV>), dim3((unsigned)nblk), dim3(64 * NWV),
-                           (size_t)lbytes + 16, s, (int)nblk, a, *g_rs_aux);
+template <int TYPE, int NI, int MC, bool XL>
+const void *rs_instance(const GemvPlan &p) {
+    const void *k = nullptr;
+    if constexpr (XL) {
+#define KCPP_RS_PICK(R_, MODE_, PRO_)                                                                                 \
+    if (p.kernel == GEMV_RS && p.R == R_ && p.mode == MODE_ && p.pro == PRO_ && !p.PF && p.waves == 8 && !p.ROUTE && !p.EX) \
+        k = (const void *)k_gemv_rs<TYPE, NI, R_, MODE_, PRO_, MC, 0, 8, true>;
+        KCPP_RS_XL_INSTANCES(KCPP_RS_PICK)
+#undef KCPP_RS_PICK
     } else {
-        hipLaunchKernelGGL((k_gemv_rs<TYPE, NI, R, MODE, PRO, MC, PF, NWV, XL, ROUTE, EX>), dim3((unsigned)nblk), dim3(64 * NWV),
-                           (size_t)lbytes + 16, s, (int)nblk, a);
+#define KCPP_RS_PICK(R_, MODE_, PRO_, PF_, NWV_, ROUTE_, EX_)                                                         \
+    if (p.kernel == GEMV_RS && p.R == R_ && p.mode == MODE_ && p.pro == PRO_ && p.PF == PF_ && p.waves == NWV_ &&     \
+        p.ROUTE == ROUTE_ && p.EX == EX_)                                                                             \
+        k = (const void *)k_gemv_rs<TYPE, NI, R_, MODE_, PRO_, MC, PF_, NWV_, false, ROUTE_, EX_>;
+        KCPP_RS_INSTANCES(KCPP_RS_PICK)
+        if constexpr (MC == 1) { KCPP_RS_PICK(1, 1, 1, 1, 8, true, false) }        // the routed two-slot GLU
+#undef KCPP_RS_PICK
+#define KCPP_RS_PICK(R_, MODE_, PRO_, PF_, NWV_)                                                                      \
+    if (p.kernel == GEMV_RS_AUX && p.R == R_ && p.mode == MODE_ && p.pro == PRO_ && p.PF == PF_ && p.waves == NWV_)   \
+        k = (const void *)k_gemv_rs_aux<TYPE, NI, R_, MODE_, PRO_, MC, PF_, NWV_>;
+        KCPP_RS_AUX_INSTANCES(KCPP_RS_PICK)
+#undef KCPP_RS_PICK
+        // MODE 3 (both MoE slots' down projections): the Mixtral class, K 14336
+        if constexpr (MC == 4 && NI == (TYPE == KT_Q6_K_RS ? 4 : 7))
+            if (p.kernel == GEMV_RS && p.mode == 3 && p.R == 1 && p.pro == 2 && p.waves == 8)
+                k = (const void *)k_gemv_rs<TYPE, NI, 1, 3, 2, 4, Q_PF, 8, Q_XL>;
     }
-    KCPP_CHECK(hipGetLastError());
-    return 0;
+    return k;
 }
 
-// rows per group, prefetch and grid per shape, from the launch sweep (tools/sweep_rs.sh, MI355X):
-//   gate|up (mode 1)  : R 1, PF, 512 workgroups     14.8 us / 66 MB
-//   q|k|v (mode 2)    : R 2, 512                     7.0 us / 14 MB
-//   head (N > 16384)  : R 2, 512                    69.4 us / 431 MB (6.2 TB/s)
-//   down (K > 8192)   : R 1, PF, 256 (Q4_K) / 512 (Q6_K)   12.5 / 15.0 us
-//   wo (quantize prologue, PRO 2): R 1, 512          (1024: every workgroup quantizes, more of them cost more)
-//   other             : R 1, 1024                    4.9 us / 9.4 MB
-template <int TYPE, int NI, int MC>
-int pick_rs(const DecArgs &a, int mode, int pro, hipStream_t s) {
-    const int64_t ntot = a.N[0] + (a.nseg > 1 ? a.N[1] : 0) + (a.nseg > 2 ? a.N[2] : 0);
-    int R = 1, PF = 0, B = 1024;
-    if (mode == 1) { PF = 1; B = 512; }
-    else if (mode == 2) { R = 2; B = 512; }
-    else if (ntot > 16384) { R = 2; B = 512; }
-    else if (a.K > 8192) { PF = TYPE == KT_Q4_K_RS; B = TYPE == KT_Q4_K_RS ? 256 : 512; }
-    else if (pro == 2) B = 512;          // wo with its quantize prologue (every workgroup quantizes the input)
-    // 8-wave workgroups, one per CU (one activation prologue shared by 8 waves instead of 4), measured per kernel in
-    // isolation (tools/stream_probe.py dec, weights rotated past the Infinity Cache): GLU 14.8 -> 14.1 us (PF),
-    // down Q4_K 11.3 -> 9.7 and Q6_K 13.6 -> 12.2 (no PF: two rows per wave, both in flight), wo 5.4 -> 4.7; in the
-    // bench's token graph down 12.0 / 13.7 -> 10.0 / 12.4 us, wo 5.3 -> 5.1, GLU unchanged: 577 -> 600 tok/s.  The
-    // q|k|v launches stay at 4 waves (8: 6.8 -> 7.4 us, 592 tok/s).
-    // the ggml plugin's fused nodes (aux: the intermediate nodes' tensors stored too), separate instances so the
-    // runtime's launches carry none of it: MUL_MAT -> ADD as the plain single-token launch below (quantize prologue,
-    // 8 waves), the SiLU GLU as KCPP_RS_P(2)'s mode 1
-    // q|k|v with bias / NeoX pairs (kcpp_gemv_rs checked the shapes): the mode-2 launch's EX instance, norm prologue
-    if (mode == 2 && dec_args_ex(a)) {
-        if (g_rs_aux || pro != 1) return -3;
-        return launch_rs<TYPE, NI, 2, 2, 1, MC, 0, 4, false, false, false, true>(a, B, s);
-    }
-    if (g_rs_aux) {
-        // with a ROPE behind the product: two rows per group (a rope pair in one lane), as the runtime's q|k|v launch
-        if (g_rs_aux->rope.out) {
-            if (mode != 0 || ntot > 16384 || ntot % 2) return -3;
-            if (pro == 2) return launch_rs<TYPE, NI, 2, 0, 2, MC, 0, 4, false, false, true>(a, 512, s);
-            if (pro == 1 && MC == 1) return launch_rs<TYPE, NI, 2, 0, 1, MC, 0, 4, false, false, true>(a, 512, s);
-            return -3;
-        }
-        if (mode == 0 && pro == 2 && ntot <= 16384) return launch_rs<TYPE, NI, 1, 0, 2, MC, 0, 8, false, false, true>(a, 256, s);
-        if (mode == 1 && a.nseg == 1 && !a.eid && !a.route_w) {
-            if (pro == 2) return launch_rs<TYPE, NI, 1, 1, 2, MC, 1, 4, false, false, true>(a, 512, s);
-            // the norm in the prologue (the runtime's GLU shape: 8 waves, group prefetch)
-            if (pro == 1 && MC == 1) return launch_rs<TYPE, NI, 1, 1, 1, MC, 1, 8, false, false, true>(a, 256, s);
-        }
-        return -3;
-    }
-    if (mode == 1 && pro == 1 && R == 1) {
-        if (a.route_w) {                  // routed two-slot GLU (MoE decode): K <= 4096 (one prologue chunk), NE <= 8
-            if constexpr (MC == 1) {
-                if (a.nseg == 2 && a.route_ne >= 2 && a.route_ne <= 8 && a.K <= 4096 && a.route_ids && a.route_wts &&
-                    (a.route_wt == KT_F32 || a.route_wt == KT_F16))
-                    return launch_rs<TYPE, NI, 1, 1, 1, MC, 1, 8, false, true>(a, 256, s);
-            }
-            return -3;
-        }
-        return launch_rs<TYPE, NI, 1, 1, 1, MC, 1, 8>(a, 256, s);
-    }
-    if (mode == 0 && pro == 2 && R == 1 && ntot <= 16384) return launch_rs<TYPE, NI, 1, 0, 2, MC, 0, 8>(a, 256, s);
-#define KCPP_RS_P(PRO_)                                                                                             \
-    if (pro == PRO_) {                                                                                              \
-        if (mode == 1) return PF ? launch_rs<TYPE, NI, 1, 1, PRO_, MC, 1>(a, B, s) : launch_rs<TYPE, NI, 1, 1, PRO_, MC, 0>(a, B, s); \
-        if (mode == 2) return launch_rs<TYPE, NI, 2, 2, PRO_, MC, 0>(a, B, s);                                                \
-        if (R == 2) return PF ? launch_rs<TYPE, NI, 2, 0, PRO_, MC, 1>(a, B, s) : launch_rs<TYPE, NI, 2, 0, PRO_, MC, 0>(a, B, s); \
-        return PF ? launch_rs<TYPE, NI, 1, 0, PRO_, MC, 1>(a, B, s) : launch_rs<TYPE, NI, 1, 0, PRO_, MC, 0>(a, B, s);             \
-    }
-    KCPP_RS_P(0)
-    KCPP_RS_P(1)
-    KCPP_RS_P(2)
-#undef KCPP_RS_P
-    return -3;
-}
-// long K (XL): the down projection of Llama-3-70B (K = 28672) and MoE experts with n_ff past 14336 (mode 0, quantize
-// or norm prologue), the same tensors read column by column from a quantized activation (pro 0: the M <= 8 prefill
-// tail and the ggml plugin's few-row MUL_MAT, gemv_cols), and the projections of models with n_embd past 14336 (GLU
-// mode 1, q|k|v mode 2 with the norm prologue).  One row per group (two for mode 2), 8-wave workgroups, no group
-// prefetch: a row's NI pieces are already 16 KB (Q4_K, K = 28672) in flight per wave, 128 KB per CU.  NI = the ceiling
-// the shape rounds up to.
-template <int TYPE, int NI>
-int pick_rs_xl(const DecArgs &a, int mode, int pro, hipStream_t s) {
-    if (g_rs_aux || (mode == 2 && dec_args_ex(a))) return -3;
-    constexpr int MC = TYPE == KT_Q6_K_RS ? NI : NI / 2;        // ceil(K / 4096) at the ceiling
-    if (mode == 0) {
-        if (pro == 2) return launch_rs<TYPE, NI, 1, 0, 2, MC, 0, 8, true>(a, 256, s);
-        if (pro == 1) return launch_rs<TYPE, NI, 1, 0, 1, MC, 0, 8, true>(a, 256, s);
-        if (pro == 0) return launch_rs<TYPE, NI, 1, 0, 0, MC, 0, 8, true>(a, 256, s);
-    } else if (mode == 1) {
-        if (a.route_w || (a.nseg != 1 && !a.eid1)) return -3;
-        if (pro == 1) return launch_rs<TYPE, NI, 1, 1, 1, MC, 0, 8, true>(a, 256, s);
-        if (pro == 0) return launch_rs<TYPE, NI, 1, 1, 0, MC, 0, 8, true>(a, 256, s);
-    } else if (mode == 2) {
-        if (pro == 1) return launch_rs<TYPE, NI, 2, 2, 1, MC, 0, 8, true>(a, 256, s);
-    }
-    return -3;
+// the (NI, MC, XL) classes built per type; rs_for_class calls f on the one the plan names (null: none)
+template <int NI_, int MC_, bool XL_ = false>
+struct RsClass { static constexpr int NI = NI_, MC = MC_; static constexpr bool XL = XL_; };
+template <class F, class... C>
+const void *rs_for_class(const GemvPlan &p, F &&f, C... c) {
+    const void *k = nullptr;
+    (void)((p.NI == C::NI && p.MC == C::MC && (bool)p.XL == C::XL ? (k = f(c), true) : false) || ...);
+    return k;
 }
 template <int TYPE>
-int dispatch_rs_xl(const DecArgs &a, int ni, int mode, int pro, hipStream_t s) {
-    if constexpr (TYPE == KT_Q6_K_RS) {
-        if (ni <= 6) return pick_rs_xl<TYPE, 6>(a, mode, pro, s);
-        return pick_rs_xl<TYPE, 8>(a, mode, pro, s);
-    } else if constexpr (TYPE == KT_Q5_K_RS) {         // 12 VGPRs per piece: spills past 10 pieces
-        return ni <= 10 ? pick_rs_xl<TYPE, 10>(a, mode, pro, s) : -3;
-    } else {
-        if (ni <= 10) return pick_rs_xl<TYPE, 10>(a, mode, pro, s);
-        if (ni <= 12) return pick_rs_xl<TYPE, 12>(a, mode, pro, s);
-        return ni <= 14 ? pick_rs_xl<TYPE, 14>(a, mode, pro, s) : -3;
-    }
+const void *rs_instance_of(const GemvPlan &p) {
+    auto f = [&](auto c) { using C = decltype(c); return rs_instance<TYPE, C::NI, C::MC, C::XL>(p); };
+    if constexpr (TYPE == KT_Q6_K_RS)
+        return rs_for_class(p, f, RsClass<1, 1>{}, RsClass<2, 2>{}, RsClass<3, 3>{}, RsClass<4, 4>{}, RsClass<6, 6, true>{},
+                            RsClass<8, 8, true>{});
+    else if constexpr (TYPE == KT_Q5_K_RS)
+        return rs_for_class(p, f, RsClass<1, 1>{}, RsClass<2, 1>{}, RsClass<3, 2>{}, RsClass<4, 2>{}, RsClass<5, 3>{}, RsClass<6, 3>{},
+                            RsClass<7, 4>{}, RsClass<10, 5, true>{});
+    else
+        return rs_for_class(p, f, RsClass<1, 1>{}, RsClass<2, 1>{}, RsClass<3, 2>{}, RsClass<4, 2>{}, RsClass<5, 3>{}, RsClass<6, 3>{},
+                            RsClass<7, 4>{}, RsClass<10, 5, true>{}, RsClass<12, 6, true>{}, RsClass<14, 7, true>{});
 }
 }  // namespace
+
+int gemv_rs_launch(const GemvPlan &p, const DecArgs &a, const AuxOut *o, hipStream_t s) {
+    const void *k = p.type == KT_Q4_K_RS   ? rs_instance_of<KT_Q4_K_RS>(p)
+                    : p.type == KT_Q5_K_RS ? rs_instance_of<KT_Q5_K_RS>(p)
+                    : p.type == KT_Q6_K_RS ? rs_instance_of<KT_Q6_K_RS>(p)
+                                           : nullptr;
+    if (p.kernel == GEMV_RS_AUX && !o) k = nullptr;
+    int nblk = (int)p.nblk;                 // the kernels' first argument: see k_gemv_rs
+    void *args[] = {&nblk, (void *)&a, (void *)o};
+    return gemv_go(k, p.nblk, p.block, p.lds_bytes, args, s);
+}
 
 // ---------------------------------------------------------------- q|k (Q4_K_RS) + v (Q6_K_RS) in one launch
 // The Q4_K_M "more bits" layers keep attn_v in Q6_K: instead of a second launch for its 1024 rows (a latency-bound
@@ -340,31 +289,18 @@ __global__ void __launch_bounds__(256) k_gemv_rs_qkv(const int kb_nblk, const De
 // q|k|v decode projection with q, k in Q4_K_RS and v in Q6_K_RS (segments 0, 1, 2): one launch.  -3 when not covered.
 extern "C" int kcpp_gemv_rs_qkv_mixed(const void *args, void *stream) {
     const DecArgs &a = *(const DecArgs *)args;
-    if (a.nseg != 3 || a.K % 256 || !kcpp_rs_supported(KT_Q4_K_RS, a.K) || !kcpp_rs_supported(KT_Q6_K_RS, a.K)) return -3;
-    if (a.N[0] % 2 || a.N[1] % 2 || a.N[2] % 2) return -5;
-    // bias / NeoX pairs (the EX instances): segments 0, 1 = q, k and 2 = v as the runtime passes them; whole heads
-    const bool ex = dec_args_ex(a);
-    if (ex && (a.role[0] != 0 || a.role[1] != 1 || a.role[2] != 2)) return -3;
-    if (ex && a.rope_neox && (a.D < 2 || a.D % 2 || a.N[0] % a.D || a.N[1] % a.D)) return -3;
-    const int nsb = (int)(a.K / 256);
-    const int nia = (nsb * 8 + 63) / 64, nib = (nsb * 4 + 63) / 64, mc = (int)((a.K + 4095) / 4096);
-    const int64_t groups = (a.N[0] + a.N[1] + a.N[2]) / 2;
-    int64_t nblk = std::min<int64_t>((groups + 3) / 4, 512);
-    nblk = std::max<int64_t>(nblk, (groups + 255) / 256);
-    const int64_t abytes = a.K + a.K / 256 * 4 + a.K / 16 * 2;
-    hipStream_t s = (hipStream_t)stream;
+    GemvMixedPlan m;
+    if (gemv_qkv_mixed_plan(gemv_shape_of(KT_Q4_K_RS, a, 2, 1, 2), &m)) return m.rc;
+    void (*k)(int, const DecArgs) = nullptr;
 #define KCPP_QKVM(A_, B_, M_)                                                                                          \
-    do {                                                                                                              \
-        if (ex) hipLaunchKernelGGL((k_gemv_rs_qkv<A_, B_, M_, true>), dim3((unsigned)nblk), dim3(256), (size_t)abytes + 16, s, (int)nblk, a); \
-        else hipLaunchKernelGGL((k_gemv_rs_qkv<A_, B_, M_>), dim3((unsigned)nblk), dim3(256), (size_t)abytes + 16, s, (int)nblk, a);         \
-    } while (0)
-    if (nia == 2 && nib == 1 && mc == 1) KCPP_QKVM(2, 1, 1);          // n_embd 4096 (Llama-3-8B)
-    else if (nia == 4 && nib == 2 && mc == 2) KCPP_QKVM(4, 2, 2);     // n_embd 8192 (Llama-3-70B)
-    else if (nia == 1 && nib == 1 && mc == 1) KCPP_QKVM(1, 1, 1);
-    else return -3;
+    if (m.NIA == A_ && m.NIB == B_ && m.MC == M_) k = m.EX ? k_gemv_rs_qkv<A_, B_, M_, true> : k_gemv_rs_qkv<A_, B_, M_>;
+    KCPP_QKVM(2, 1, 1)          // n_embd 4096 (Llama-3-8B)
+    KCPP_QKVM(4, 2, 2)          // n_embd 8192 (Llama-3-70B)
+    KCPP_QKVM(1, 1, 1)
 #undef KCPP_QKVM
-    KCPP_CHECK(hipGetLastError());
-    return 0;
+    int nblk = (int)m.nblk;
+    void *ka[] = {&nblk, (void *)&a};
+    return gemv_go((const void *)k, m.nblk, m.block, m.lds_bytes, ka, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------- q (RS layout) + k|v (Q8_0) in one launch
@@ -397,140 +333,39 @@ __global__ void __launch_bounds__(256) k_gemv_qkv_dual(const DecArgs a, const De
     }
 }
 
-// qa: the RS-layout segments (mode 2, rms_norm prologue) -- pick_rs's launch for them; kv: Q8_0 segments (mode 2) --
-// dispatch_mode<KT_Q8_0>'s.  -3 when the pair is not covered (the caller launches them separately).
+// qa: the RS-layout segments (mode 2, rms_norm prologue), kv: Q8_0 segments (mode 2): the two halves of
+// gemv_qkv_dual_plan.  -3 when the pair is not covered (the caller launches them separately).
 extern "C" int kcpp_gemv_qkv_dual(const void *qargs, int qtype, const void *kvargs, void *stream) {
     const DecArgs &a = *(const DecArgs *)qargs;
     const DecArgs &b = *(const DecArgs *)kvargs;
-    if (qtype != KT_Q4_K_RS && qtype != KT_Q5_K_RS && qtype != KT_Q6_K_RS) return -3;
-    if (a.K != b.K || a.K % 256 || a.K > 4096 || !kcpp_rs_supported(qtype, a.K) || a.route_w) return -3;
-    if (dec_args_ex(a) || dec_args_ex(b)) return -3;     // bias / NeoX pairs: not in this grid (the caller falls back)
-    int64_t na_rows = 0;
-    for (int i = 0; i < a.nseg; ++i) {
-        if (a.N[i] % 2) return -5;
-        na_rows += a.N[i];
-    }
-    for (int i = 0; i < b.nseg; ++i)
-        if (b.N[i] % 2) return -5;
-    // RS side: launch_rs<.., R 2, mode 2, PRO 1, .., NWV 4>(a, 512)
-    const int64_t groups = na_rows / 2;
-    int64_t nA = std::min<int64_t>((groups + 3) / 4, 512);
-    nA = std::max<int64_t>(nA, (groups + 255) / 256);
-    const int64_t abytes = a.K + a.K / 256 * 4 + a.K / 16 * 2;
-    // Q8_0 side: launch_dec_it<KT_Q8_0, 2, 2, 1, 1, IT>
-    size_t ldsB = 0;
-    const int64_t nB = dec_grid<KT_Q8_0, 2, 1>(b, ldsB);
-    const int64_t upr = b.K / Unit<KT_Q8_0>::ELEMS, itb = (upr + 63) / 64;
-    const size_t lds = std::max<size_t>((size_t)abytes + 16, ldsB);
-    const int nsb = (int)(a.K / 256);
-    const int ppsb = qtype == KT_Q6_K_RS ? 4 : 8;
-    const int nia = (nsb * ppsb + 63) / 64;
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)(nA + nB));
-#define KCPP_DUAL(TA_, NIA_, ITB_) hipLaunchKernelGGL((k_gemv_qkv_dual<TA_, NIA_, 1, ITB_>), grid, dim3(256), lds, s, a, b, (int)nA)
-    if (itb == 2 && nia == 2 && qtype == KT_Q5_K_RS) KCPP_DUAL(KT_Q5_K_RS, 2, 2);      // Mixtral: K 4096
-    else if (itb == 2 && nia == 2 && qtype == KT_Q4_K_RS) KCPP_DUAL(KT_Q4_K_RS, 2, 2);
-    else if (itb == 2 && nia == 1 && qtype == KT_Q6_K_RS) KCPP_DUAL(KT_Q6_K_RS, 1, 2);
-    else return -3;
-#undef KCPP_DUAL
-    KCPP_CHECK(hipGetLastError());
-    return 0;
+    GemvDualPlan d;
+    if (gemv_qkv_dual_plan(gemv_shape_of(qtype, a, 2, 1, 2), gemv_shape_of(KT_Q8_0, b, 2, 1, 2), &d)) return d.rc;
+    void (*k)(const DecArgs, const DecArgs, int) = nullptr;
+    if (d.b.IT == 2 && d.a.NI == 2 && qtype == KT_Q5_K_RS) k = k_gemv_qkv_dual<KT_Q5_K_RS, 2, 1, 2>;      // Mixtral: K 4096
+    if (d.b.IT == 2 && d.a.NI == 2 && qtype == KT_Q4_K_RS) k = k_gemv_qkv_dual<KT_Q4_K_RS, 2, 1, 2>;
+    if (d.b.IT == 2 && d.a.NI == 1 && qtype == KT_Q6_K_RS) k = k_gemv_qkv_dual<KT_Q6_K_RS, 1, 1, 2>;
+    int nA = (int)d.a.nblk;
+    void *ka[] = {(void *)&a, (void *)&b, &nA};
+    return gemv_go((const void *)k, d.nblk, 256, d.lds_bytes, ka, (hipStream_t)stream);
 }
 
-// K coverage of the RS kernels (the runtime picks an RS layout only where this holds): activation slices in registers
-// up to 56 (Q4_K / Q5_K) / 64 (Q6_K) super-blocks; read from LDS (XL, one row's pieces in flight per wave) up to the
-// register budget of a row: 112 (Q4_K: K 28672, Llama-3-70B's n_ff), 80 (Q5_K), 128 (Q6_K) super-blocks
-extern "C" int kcpp_rs_supported(int type, int64_t K) {
-    if (K % 256 || K < 256) return 0;
-    const int64_t nsb = K / 256;
-    if (type == KT_Q4_K_RS || type == KT_Q4_K) return nsb <= 112;
-    if (type == KT_Q5_K_RS || type == KT_Q5_K) return nsb <= 80;
-    if (type == KT_Q6_K_RS || type == KT_Q6_K) return nsb % 8 == 0 && nsb <= 128;
-    return 0;
-}
+// K coverage of the RS kernels (the runtime picks an RS layout only where this holds): gemv_plan.h gemv_rs_supported
+extern "C" int kcpp_rs_supported(int type, int64_t K) { return gemv_rs_supported(type, K); }
 
-#ifndef Q_PF
-#define Q_PF 0               // MODE 3 group prefetch: measured no faster (23.2 / 21.7 vs 23.2 / 21.0 us), more registers
-#endif
-#ifndef Q_XL
-#define Q_XL false
-#endif
-// MODE 3 (both MoE slots' down projections): the shapes of the Mixtral class (n_ff 14336: 56 super-blocks)
-static int pick_rs_pair(int type, const DecArgs &a, hipStream_t s) {
-    if (a.nseg != 1 || !a.eid || !a.eid1 || !a.escale || a.K != 14336) return -3;
-    if (type == KT_Q4_K_RS) return launch_rs<KT_Q4_K_RS, 7, 1, 3, 2, 4, Q_PF, 8, Q_XL>(a, 256, s);
-    if (type == KT_Q5_K_RS) return launch_rs<KT_Q5_K_RS, 7, 1, 3, 2, 4, Q_PF, 8, Q_XL>(a, 256, s);
-    if (type == KT_Q6_K_RS) return launch_rs<KT_Q6_K_RS, 4, 1, 3, 2, 4, Q_PF, 8, Q_XL>(a, 256, s);
-    return -3;
-}
-
-// -3 = not covered
+// the plan restricted to the RS kernels; -3 = not covered
 extern "C" int kcpp_gemv_rs(int type, const void *args, int mode, int pro, void *stream) {
     const DecArgs &a = *(const DecArgs *)args;
-    hipStream_t s = (hipStream_t)stream;
-    if (mode == 3) return pro == 2 && kcpp_rs_supported(type, a.K) ? pick_rs_pair(type, a, s) : -3;
-    if (a.nseg < 1 || a.nseg > 3 || !kcpp_rs_supported(type, a.K)) return -3;
-    if (mode == 1 && a.nseg != 1 && !(a.nseg == 2 && (a.eid1 || a.route_w))) return -3;   // GLU: one segment, or two MoE slots
-    if (mode == 2 && dec_args_ex(a)) {      // bias / NeoX pairs: dense weights; NeoX groups are pairs inside whole heads
-        if (a.eid || a.route_w) return -3;
-        for (int i = 0; i < a.nseg; ++i) {
-            if (a.role[i] < 0 || a.role[i] > 2) return -3;
-            if (a.rope_neox && a.role[i] != 2 && (a.D < 2 || a.D % 2 || a.N[i] % a.D)) return -3;
-        }
-    }
-    const int nsb = (int)(a.K / 256);
-    if (type == KT_Q4_K_RS) {
-        const int ni = (nsb * 8 + 63) / 64, mc = (int)((a.K + 4095) / 4096);
-        switch (ni) {
-        case 1: return pick_rs<KT_Q4_K_RS, 1, 1>(a, mode, pro, s);
-        case 2: return pick_rs<KT_Q4_K_RS, 2, 1>(a, mode, pro, s);
-        case 3: return pick_rs<KT_Q4_K_RS, 3, 2>(a, mode, pro, s);
-        case 4: return pick_rs<KT_Q4_K_RS, 4, 2>(a, mode, pro, s);
-        case 5: return pick_rs<KT_Q4_K_RS, 5, 3>(a, mode, pro, s);
-        case 6: return pick_rs<KT_Q4_K_RS, 6, 3>(a, mode, pro, s);
-        case 7: return pick_rs<KT_Q4_K_RS, 7, 4>(a, mode, pro, s);
-        default: return dispatch_rs_xl<KT_Q4_K_RS>(a, ni, mode, pro, s);
-        }
-    }
-    if (type == KT_Q5_K_RS) {
-        const int ni = (nsb * 8 + 63) / 64, mc = (int)((a.K + 4095) / 4096);
-        switch (ni) {
-        case 1: return pick_rs<KT_Q5_K_RS, 1, 1>(a, mode, pro, s);
-        case 2: return pick_rs<KT_Q5_K_RS, 2, 1>(a, mode, pro, s);
-        case 3: return pick_rs<KT_Q5_K_RS, 3, 2>(a, mode, pro, s);
-        case 4: return pick_rs<KT_Q5_K_RS, 4, 2>(a, mode, pro, s);
-        case 5: return pick_rs<KT_Q5_K_RS, 5, 3>(a, mode, pro, s);
-        case 6: return pick_rs<KT_Q5_K_RS, 6, 3>(a, mode, pro, s);
-        case 7: return pick_rs<KT_Q5_K_RS, 7, 4>(a, mode, pro, s);
-        default: return dispatch_rs_xl<KT_Q5_K_RS>(a, ni, mode, pro, s);
-        }
-    }
-    if (type == KT_Q6_K_RS) {
-        const int ni = (nsb * 4 + 63) / 64;
-        switch (ni) {
-        case 1: return pick_rs<KT_Q6_K_RS, 1, 1>(a, mode, pro, s);
-        case 2: return pick_rs<KT_Q6_K_RS, 2, 2>(a, mode, pro, s);
-        case 3: return pick_rs<KT_Q6_K_RS, 3, 3>(a, mode, pro, s);
-        case 4: return pick_rs<KT_Q6_K_RS, 4, 4>(a, mode, pro, s);
-        default: return dispatch_rs_xl<KT_Q6_K_RS>(a, ni, mode, pro, s);
-        }
-    }
-    return -3;
+    GemvPlan p;
+    if (gemv_plan(gemv_shape_of(type, a, mode, pro, 0), GEMV_ENTRY_RS, &p)) return p.rc;
+    return gemv_rs_launch(p, a, nullptr, (hipStream_t)stream);
 }
 
-// the ggml plugin's fused nodes: kcpp_gemv_rs's launch (modes 0 and 1, quantize prologue, one segment) through the AUX
-// instances, which also store the intermediate nodes' tensors (AuxOut); -3 where no AUX instance covers the shape
+// the ggml plugin's fused nodes: the AUX instances, which also store the intermediate nodes' tensors (AuxOut); the
+// prologue is the norm when DecArgs.nw is set (x = the norm's input, nw = the MUL's weight), else quantize only;
+// -3 where no AUX instance covers the shape
 extern "C" int kcpp_gemv_rs_aux(int type, const void *args, int mode, const AuxOut *aux, void *stream) {
-    if (!aux || (mode == 0 && !aux->p0 && !aux->h0 && !aux->rope.out) || (mode == 1 && (!aux->p0 || !aux->p1 || !aux->p2)) ||
-        (mode != 0 && mode != 1) || (aux->rope.out && (mode != 0 || !aux->rope.pos || aux->rope.D < 2 || aux->rope.D % 2)))
-        return -3;
-    // the norm prologue (rn / yn given): x = the norm's input, nw = the MUL's weight, K <= 4096 (one chunk per thread,
-    // so the prologue's sum order is the plugin's norm kernels' -- ggml_ops.hip row_sumsq16)
-    const DecArgs &da = *(const DecArgs *)args;
-    const bool pro1 = da.nw != nullptr;       // (only the plugin's norm-in launches set nw here)
-    if (pro1 && (da.K > 4096 || da.K % 256)) return -3;
-    g_rs_aux = aux;
-    const int rc = kcpp_gemv_rs(type, args, mode, pro1 ? 1 : 2, stream);
-    g_rs_aux = nullptr;
-    return rc;
+    const DecArgs &a = *(const DecArgs *)args;
+    GemvPlan p;
+    if (gemv_plan(gemv_shape_of(type, a, mode, 0, 0, aux), GEMV_ENTRY_RS_AUX, &p)) return p.rc;
+    return gemv_rs_launch(p, a, aux, (hipStream_t)stream);
 }

@@ -293,37 +293,18 @@ __global__ void __launch_bounds__(256) k_gemv_stream(const DecArgs a) {
     }
 }
 
-namespace {
-
-template <int LPR, int NI, int MODE, int PRO, int MC>
-int launch_stream(const DecArgs &a, hipStream_t s) {
-    constexpr int G = 64 / LPR;
-    const int64_t K = a.K, nsb = K / 256;
-    int64_t ntot = 0;
-    for (int i = 0; i < a.nseg; ++i) {
-        if (a.N[i] % G) return -5;
-        ntot += a.N[i];
-    }
-    const int64_t tiles = ntot / G;
-    int64_t nblk = std::min<int64_t>((tiles + 3) / 4, 1024);
-    nblk = std::max<int64_t>(nblk, (tiles + 4 * LPR - 1) / (4 * LPR));   // <= LPR tiles per wave (slots)
-    const int64_t abytes = K + nsb * 4 + (K / 16) * 2;
-    const size_t lds = (size_t)((abytes + 15) & ~15) + (size_t)4 * (MODE == 1 ? 2 : 1) * G * nsb * (16 + 4);
-    hipLaunchKernelGGL((k_gemv_stream<LPR, NI, MODE, PRO, MC>), dim3((unsigned)nblk), dim3(256), lds, s, a);
-    KCPP_CHECK(hipGetLastError());
-    return 0;
+// The built instance (LPR, NI, MODE, PRO, MC): the one the plan's GEMV_STREAM rule names (gemv_plan.h)
+int gemv_stream_launch(const GemvPlan &p, const DecArgs &a, hipStream_t s) {
+    void (*k)(const DecArgs) = nullptr;
+    if (p.LPR == 64 && p.NI == 8 && p.mode == 0 && p.pro == 2 && p.MC == 4) k = k_gemv_stream<64, 8, 0, 2, 4>;
+    void *args[] = {(void *)&a};
+    return gemv_go(p.kernel == GEMV_STREAM ? (const void *)k : nullptr, p.nblk, p.block, p.lds_bytes, args, s);
 }
 
-}  // namespace
-
-// Returns -3 when the shape/type is not covered (the caller falls back to kcpp_gemv_dec).
+// the plan restricted to this kernel; -3 = not covered
 extern "C" int kcpp_gemv_stream(int type, const void *args, int mode, int pro, void *stream) {
     const DecArgs &a = *(const DecArgs *)args;
-    hipStream_t s = (hipStream_t)stream;
-    if (type != KT_Q4_K || a.K % 256 || a.nseg < 1 || a.nseg > 3 || a.eid) return -3;
-    if (mode == 2 && dec_args_ex(a)) return -3;          // q|k|v bias / NeoX pairs: the RS kernels only
-    // measured (tools/stream_probe.py): only the K = 14336 quantize-prologue shape (ffn_down in the kcpp Q4_K
-    // layout) beats the unit-per-lane kernel (20.3 vs 24.6 us); at K = 4096 it loses on VALU work per byte
-    if (a.K == 14336 && mode == 0 && pro == 2) return launch_stream<64, 8, 0, 2, 4>(a, s);   // one row per wave
-    return -3;
+    GemvPlan p;
+    if (gemv_plan(gemv_shape_of(type, a, mode, pro, 0), GEMV_ENTRY_STREAM, &p)) return p.rc;
+    return gemv_stream_launch(p, a, (hipStream_t)stream);
 }

@@ -955,7 +955,7 @@ bool compute_node(BackendCtx *bc, kggml_tensor *n) {
             memset(&d, 0, sizeof d);
             d.K = K; d.nseg = 1; d.W[0] = (const uint8_t *)W; d.N[0] = N; d.Y[0] = (float *)n->data;
             d.x = (const float *)b->data;
-            if (kcpp_gemv_dec(tt, &d, 0, 2, N > 16384 ? 4 : (N > 4096 ? 2 : 1), s) == 0) return true;
+            if (kcpp_gemv_dec(tt, &d, 0, 2, gemv_rows_per_wave(N, 0), s) == 0) return true;
             (void)hipGetLastError();            // not covered (type / shape): the two-launch path below
         }
         void *act = bc->act.get((size_t)kcpp_act_bytes(a->type, K, M) + 256);

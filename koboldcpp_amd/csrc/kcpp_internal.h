@@ -3,6 +3,7 @@
 #include <stdint.h>
 
 #include "fa_plan.h"     // KCPP_FA_WS_HEADER, the attention launch plans
+#include "gemv_plan.h"   // the fused decode mat-vec's launch plans
 // single-token decode attention: contexts up to this many keys would run the one-launch kernel (attn_dec.hip fa_short_launch;
 // off: one workgroup per kv head measured slower than the split pair at every size, 10.3 vs 7.8 us at 300 keys;
 // runtime.cpp picks the regime per step, KCPP_FA_SHORT overrides)
@@ -27,6 +28,8 @@ int kcpp_vec_dot_type(int wtype);
 }
 #include "../../include/kcpp_mi355x.h"
 #include <hip/hip_runtime.h>
+
+#include "kcpp_common.h"     // KCPP_CHECK
 
 // arguments of the fused decode mat-vec (gemv_dec.hip)
 struct DecArgs {
@@ -72,8 +75,8 @@ struct DecArgs {
     float *route_wts;
     // MODE 2 (Qwen2 class): bias[i] (f32 [N[i]], may be null) is added to segment i's product before the rotation /
     // the V store; rope_neox: the q / k rotation pairs rows (j, j + D/2) of a head (ggml's NeoX mode) instead of
-    // (2j, 2j + 1).  All zero = no bias, NORM pairs.  Only the RS kernels (gemv_rs.hip) take them: every other
-    // mode-2 implementation answers -3 when one is set.
+    // (2j, 2j + 1).  All zero = no bias, NORM pairs.  Only the RS kernels (gemv_rs.hip) take them: the plan
+    // (gemv_plan.h) answers -3 for every other mode-2 kernel when one is set.
     const float *bias[3];
     int rope_neox;
 };
@@ -151,10 +154,38 @@ __device__ __forceinline__ int64_t dec_expert_offset(const DecArgs &a, const int
     if (a.n_exp > 0) e = e < 0 ? 0 : (e >= (int)a.n_exp ? (int)a.n_exp - 1 : e);
     return (int64_t)e * a.ebytes;
 }
+// the plan's view of a call (gemv_plan.h): the one place that looks at the pointers
+static inline GemvShape gemv_shape_of(int type, const DecArgs &a, int mode, int pro, int rows_per_wave, const AuxOut *o = nullptr) {
+    GemvShape s{};
+    s.type = type, s.K = a.K, s.nseg = a.nseg, s.D = a.D;
+    for (int i = 0; i < 3; ++i) s.N[i] = a.N[i], s.role[i] = a.role[i];
+    s.mode = mode, s.pro = pro, s.rows_per_wave = rows_per_wave;
+    s.route_wt = a.route_wt, s.route_ne = a.route_ne;
+    s.flags = (a.eid ? GEMV_F_EID : 0) | (a.eid1 ? GEMV_F_EID1 : 0) | (a.escale ? GEMV_F_ESCALE : 0) |
+              (a.route_w ? GEMV_F_ROUTE_W : 0) | (a.route_ids && a.route_wts ? GEMV_F_ROUTE_OUT : 0) |
+              (dec_args_ex(a) ? GEMV_F_EX : 0) | (a.rope_neox ? GEMV_F_NEOX : 0) | (a.nw ? GEMV_F_NW : 0);
+    if (o)
+        s.flags |= GEMV_F_AUX | (o->p0 || o->h0 ? GEMV_F_AUX_P0H0 : 0) | (o->p0 && o->p1 && o->p2 ? GEMV_F_AUX_GLU : 0) |
+                   (o->rope.out ? GEMV_F_AUX_ROPE : 0) | (o->rope.pos && o->rope.D >= 2 && o->rope.D % 2 == 0 ? GEMV_F_AUX_ROPE_OK : 0);
+    return s;
+}
+// the kernel files' launchers: the plan's instance through the file's list of built instances (GEMV_ERR_NO_INSTANCE
+// when the plan names none; tests/test_gemv_plan.py shows it never does)
+int gemv_rs_launch(const GemvPlan &p, const DecArgs &a, const AuxOut *o, hipStream_t s);     // GEMV_RS, GEMV_RS_AUX
+int gemv_q4k_launch(const GemvPlan &p, const DecArgs &a, hipStream_t s);
+int gemv_stream_launch(const GemvPlan &p, const DecArgs &a, hipStream_t s);
+template <int TYPE> int gemv_unit_launch(const GemvPlan &p, const DecArgs &a, hipStream_t s);  // one TU per type
+// the launch itself: the instance a launcher's list matched (null: none), the plan's grid, block and LDS; args = the
+// addresses of the kernel's arguments in order
+static inline int gemv_go(const void *kernel, int64_t nblk, int block, int64_t lds_bytes, void **args, hipStream_t s) {
+    if (!kernel) return GEMV_ERR_NO_INSTANCE;
+    KCPP_CHECK(hipLaunchKernel(kernel, dim3((unsigned)nblk), dim3((unsigned)block), args, (size_t)lds_bytes, s));
+    return 0;
+}
+// what a call runs: gemv_plan.h's rules block
 extern "C" int kcpp_gemv_dec(int type, const void *args, int mode, int pro, int rows_per_wave, void *stream);
-// coalesced Q4_K variant (gemv_stream.hip); -3 = not covered
+// the single families' entries: the same plan restricted to one kernel; -3 = not covered
 extern "C" int kcpp_gemv_stream(int type, const void *args, int mode, int pro, void *stream);
-// VALU-lean unit-per-lane Q4_K variant (gemv_q4k.hip); -3 = not covered
 extern "C" int kcpp_gemv_q4k(const void *args, int mode, int pro, void *stream);
 
 

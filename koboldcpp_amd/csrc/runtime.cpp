@@ -997,11 +997,6 @@ static int matmul(kcpp_model *m, const KTensor &W, const KTensor *W2, const void
     return gemm_w(W, W2, act, M, Y, ldy, res, ldr, mode, m->gemm_ws, m->stream);
 }
 
-static int rows_per_wave(int64_t N, int mode) {
-    if (mode == 1) return 1;
-    return N > 16384 ? 4 : (N > 4096 ? 2 : 1);
-}
-
 // MoE FFN for one token (llm_build_moe_ffn, src/llama.cpp:9416-9514), entirely on the device:
 // ffn_norm -> router/softmax/top-k on the GPU (moe_ids, moe_w), then per top-k slot j the expert's
 // gate|up and down mat-vecs read their expert index from moe_ids[j] (DecArgs.eid) and down writes
@@ -1029,7 +1024,7 @@ static int moe_dec(kcpp_model *m, const KLayer &L) {
         a.n_exp = hp.n_expert; a.ebytes = (int64_t)t[6].slice_bytes;
         a.route_w = t[9].d; a.route_wt = t[9].type; a.route_ne = (int)hp.n_expert;
         a.route_ids = m->moe_ids; a.route_wts = m->moe_w;
-        const int rc = kcpp_gemv_dec(t[6].type, &a, 1, 1, rows_per_wave(F, 1), s);
+        const int rc = kcpp_gemv_dec(t[6].type, &a, 1, 1, gemv_rows_per_wave(F, 1), s);
         if (rc != 0 && rc != -3) return rc;
         routed = rc == 0;
         m->n_fused_route += routed;
@@ -1079,7 +1074,7 @@ static int moe_dec(kcpp_model *m, const KLayer &L) {
         a.W[0] = a.W[1] = (const uint8_t *)t[6].d; a.W2 = (const uint8_t *)t[7].d; a.N[0] = a.N[1] = F;
         a.Y[0] = m->h; a.Y[1] = m->h + F;
         a.eid = m->moe_ids; a.eid1 = m->moe_ids + 1; a.n_exp = hp.n_expert; a.ebytes = (int64_t)t[6].slice_bytes;
-        RC(kcpp_gemv_dec(t[6].type, &a, 1, 1, rows_per_wave(F, 1), s));
+        RC(kcpp_gemv_dec(t[6].type, &a, 1, 1, gemv_rows_per_wave(F, 1), s));
     }
     // RS down projections of both slots in one launch (k_gemv_rs MODE 3: half the waves per slot, met in LDS):
     // ((w0 o0) + (w1 o1)) + x, the two chained launches' result bit for bit
@@ -1090,7 +1085,7 @@ static int moe_dec(kcpp_model *m, const KLayer &L) {
         a.W[0] = a.W[1] = (const uint8_t *)t[8].d; a.N[0] = E; a.Y[0] = m->x; a.res = m->x;
         a.eid = m->moe_ids; a.eid1 = m->moe_ids + 1; a.n_exp = hp.n_expert; a.ebytes = (int64_t)t[8].slice_bytes;
         a.escale = m->moe_w;
-        const int rc = kcpp_gemv_dec(t[8].type, &a, 3, 2, rows_per_wave(E, 0), s);
+        const int rc = kcpp_gemv_dec(t[8].type, &a, 3, 2, gemv_rows_per_wave(E, 0), s);
         if (rc == 0) { m->n_pair_down++; return 0; }
         if (rc != -3) return rc;
     }
@@ -1102,7 +1097,7 @@ static int moe_dec(kcpp_model *m, const KLayer &L) {
             a.K = E; a.x = m->x; a.nw = (const float *)t[5].d; a.eps = hp.eps; a.nseg = 1;
             a.W[0] = (const uint8_t *)t[6].d; a.W2 = (const uint8_t *)t[7].d; a.N[0] = F; a.Y[0] = m->h;
             a.eid = m->moe_ids + j; a.n_exp = hp.n_expert; a.ebytes = (int64_t)t[6].slice_bytes;
-            RC(kcpp_gemv_dec(t[6].type, &a, 1, 1, rows_per_wave(F, 1), s));
+            RC(kcpp_gemv_dec(t[6].type, &a, 1, 1, gemv_rows_per_wave(F, 1), s));
         } else {
             for (int i = 6; i <= 7; ++i) {
                 DecArgs a;
@@ -1110,7 +1105,7 @@ static int moe_dec(kcpp_model *m, const KLayer &L) {
                 a.K = E; a.x = m->x; a.nw = (const float *)t[5].d; a.eps = hp.eps; a.nseg = 1;
                 a.W[0] = (const uint8_t *)t[i].d; a.N[0] = F; a.Y[0] = i == 6 ? m->h : m->qkv;
                 a.eid = m->moe_ids + j; a.n_exp = hp.n_expert; a.ebytes = (int64_t)t[i].slice_bytes;
-                RC(kcpp_gemv_dec(t[i].type, &a, 0, 1, rows_per_wave(F, 0), s));
+                RC(kcpp_gemv_dec(t[i].type, &a, 0, 1, gemv_rows_per_wave(F, 0), s));
             }
             RC(kcpp_silu_mul(m->h, m->h, m->qkv, F, s));
         }
@@ -1124,7 +1119,7 @@ static int moe_dec(kcpp_model *m, const KLayer &L) {
             a.pre = j > 0 ? m->moe_slots : nullptr;
             a.res = j == NU - 1 ? m->x : nullptr;
         }
-        const int rc = kcpp_gemv_dec(t[8].type, &a, 0, 2, rows_per_wave(E, 0), s);
+        const int rc = kcpp_gemv_dec(t[8].type, &a, 0, 2, gemv_rows_per_wave(E, 0), s);
         if (rc == -8) {
             // n_ff beyond the fused kernels' budget (no RS layout for it: chain is false, slots + combine): quantize the
             // slot's h once, then the generic expert mat-vec (device-resident expert id, times the router weight)
@@ -1290,7 +1285,7 @@ static int qkv_dec_unfused(kcpp_model *m, KLayer &L, const KTensor *t) {
         memset(&a, 0, sizeof a);
         a.K = E; a.nseg = 1; a.W[0] = (const uint8_t *)t[j].d; a.N[0] = t[j].N; a.Y[0] = y;
         a.act = (const uint8_t *)m->act;
-        int rc = kcpp_gemv_dec(t[j].type, &a, 0, 0, rows_per_wave(t[j].N, 0), s);
+        int rc = kcpp_gemv_dec(t[j].type, &a, 0, 0, gemv_rows_per_wave(t[j].N, 0), s);
         if (rc == -3 || rc == -8) rc = kcpp_gemv(t[j].type, t[j].d, nullptr, E, t[j].N, m->act, 1, y, t[j].N, nullptr, 0, 0, s);
         RC(rc);
     }
@@ -1374,11 +1369,11 @@ static int forward_layers_dec(kcpp_model *m) {
             a.K = E; a.nseg = 1;
             a.W[0] = (const uint8_t *)t[4].d; a.N[0] = t[4].N; a.Y[0] = m->x; a.res = m->x;
             a.x = m->attn;
-            int rc = kcpp_gemv_dec(t[4].type, &a, 0, 2, rows_per_wave(t[4].N, 0), s);
+            int rc = kcpp_gemv_dec(t[4].type, &a, 0, 2, gemv_rows_per_wave(t[4].N, 0), s);
             if (rc == -3) {
                 RC(kcpp_quantize_act(kcpp_vec_dot_type(t[4].type), m->attn, E, m->act, E, 1, s));
                 a.x = nullptr; a.act = (const uint8_t *)m->act;
-                rc = kcpp_gemv_dec(t[4].type, &a, 0, 0, rows_per_wave(t[4].N, 0), s);
+                rc = kcpp_gemv_dec(t[4].type, &a, 0, 0, gemv_rows_per_wave(t[4].N, 0), s);
             }
             RC(rc);
         }
@@ -1389,14 +1384,14 @@ static int forward_layers_dec(kcpp_model *m) {
             memset(&a, 0, sizeof a);
             a.K = E; a.x = m->x; a.nw = (const float *)t[5].d; a.eps = hp.eps; a.nseg = 1;
             a.W[0] = (const uint8_t *)t[6].d; a.W2 = (const uint8_t *)t[7].d; a.N[0] = F; a.Y[0] = m->h;
-            RC(kcpp_gemv_dec(t[6].type, &a, 1, 1, rows_per_wave(F, 1), s));
+            RC(kcpp_gemv_dec(t[6].type, &a, 1, 1, gemv_rows_per_wave(F, 1), s));
         } else {
             for (int j = 6; j <= 7; ++j) {
                 DecArgs a;
                 memset(&a, 0, sizeof a);
                 a.K = E; a.x = m->x; a.nw = (const float *)t[5].d; a.eps = hp.eps; a.nseg = 1;
                 a.W[0] = (const uint8_t *)t[j].d; a.N[0] = F; a.Y[0] = j == 6 ? m->h : m->qkv;
-                RC(kcpp_gemv_dec(t[j].type, &a, 0, 1, rows_per_wave(F, 0), s));
+                RC(kcpp_gemv_dec(t[j].type, &a, 0, 1, gemv_rows_per_wave(F, 0), s));
             }
             RC(kcpp_silu_mul(m->h, m->h, m->qkv, F, s));
         }
@@ -1405,7 +1400,7 @@ static int forward_layers_dec(kcpp_model *m) {
             memset(&a, 0, sizeof a);
             a.K = F; a.x = m->h; a.nseg = 1;
             a.W[0] = (const uint8_t *)t[8].d; a.N[0] = E; a.Y[0] = m->x; a.res = m->x;
-            const int rc = kcpp_gemv_dec(t[8].type, &a, 0, 2, rows_per_wave(E, 0), s);
+            const int rc = kcpp_gemv_dec(t[8].type, &a, 0, 2, gemv_rows_per_wave(E, 0), s);
             if (rc == -8) {   // K-slices beyond the fused kernel's register budget (very large n_ff)
                 RC(kcpp_quantize_act(kcpp_vec_dot_type(t[8].type), m->h, F, m->act2, F, 1, s));
                 RC(kcpp_gemv(t[8].type, t[8].d, nullptr, F, E, m->act2, 1, m->x, E, m->x, E, 0, s));
@@ -1422,7 +1417,7 @@ static int head_dec(kcpp_model *m) {
     memset(&a, 0, sizeof a);
     a.K = m->hp.n_embd; a.x = m->x; a.nw = (const float *)m->output_norm.d; a.eps = m->hp.eps; a.nseg = 1;
     a.W[0] = (const uint8_t *)(m->output.dec ? m->output.dec : m->output.d); a.N[0] = m->hp.n_vocab; a.Y[0] = m->logits;
-    return kcpp_gemv_dec(m->output.dec ? KT_Q8_0 : m->output.type, &a, 0, 1, rows_per_wave(m->hp.n_vocab, 0), m->stream);
+    return kcpp_gemv_dec(m->output.dec ? KT_Q8_0 : m->output.type, &a, 0, 1, gemv_rows_per_wave(m->hp.n_vocab, 0), m->stream);
 }
 
 // run layers [il0, il1) on m->x for T tokens (T <= ub).  n_past via pos_dev when graph-replayed.

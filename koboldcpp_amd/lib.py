@@ -70,6 +70,9 @@ _SIGS = {
     "kcpp_fa_split_ws_bytes": [I],
     "kcpp_fa_prefill_plan": [I, I, I, I, I, I, P],
     "kcpp_fa_decode_plan": [I, I, I, I, I, I, I, I, I, I, P],
+    "kcpp_gemv_dec_plan": [I, I, I64, I, I64, I64, I64, I, I, I, I, I, I, I, I, I, I, P],
+    "kcpp_gemv_qkv_mixed_plan": [I64, I64, I64, I64, I, I, I, I, I, P],
+    "kcpp_gemv_qkv_dual_plan": [I, I64, I, P, I, I64, I, P, I, P],
     "kcpp_flash_attn_dec_ta": [P, P, P, P, P, P, I, I, I, I, P, I, Fl, P],
     "kcpp_fa_decode_ex": [P, P, P, I64, I64, P, P, P, I, I, I, P, I, Fl, I, P],
     "kcpp_fa_set_stamps": [P],
@@ -520,6 +523,55 @@ def fa_decode_plan(form, T, H, HKV, D=128, nkv=1, n_rows=0, qkind=0, sel=0, cap=
         d[k] = (v[11 + 2 * i] & 0xFFFFFFFF) | (v[12 + 2 * i] << 32)
     d["kernel"] = FA_DEC_KERNEL[d["kernel"]]
     return d
+
+
+GEMV_KERNEL = ("rs", "rs_aux", "q4k", "stream", "unit")
+GEMV_ENTRY = ("dec", "rs", "rs_aux", "q4k", "stream", "unit")
+# what a DecArgs / AuxOut hold (gemv_plan.h GEMV_F_*)
+GEMV_FLAGS = {"eid": 1, "eid1": 2, "escale": 4, "route_w": 8, "route_out": 16, "ex": 32, "neox": 64, "nw": 128, "aux": 256,
+              "aux_p0h0": 512, "aux_glu": 1024, "aux_rope": 2048, "aux_rope_ok": 4096}
+_GEMV_PLAN_FIELDS = ("rc", "kernel", "type", "mode", "pro", "NI", "IT", "LPR", "R", "MC", "PF", "waves", "XL", "ROUTE", "EX",
+                     "block", "nblk", "lds_bytes")
+
+
+def _gemv_flags(flags):
+    return sum(GEMV_FLAGS[f] for f in flags)
+
+
+def gemv_dec_plan(entry, wtype, K, N, mode, pro, rows_per_wave=1, flags=(), role=(0, 1, 2), D=0, route_wt=0, route_ne=0):
+    """what a fused single-token mat-vec entry runs (kcpp_gemv_dec_plan; host only).  entry: a GEMV_ENTRY name; N: the
+    segments' row counts; flags: GEMV_FLAGS names.  Returns the entry's error code (a negative int), or a dict of kernel
+    (a GEMV_KERNEL name), the instance parameters type, mode, pro, NI, IT, LPR, R, MC, PF, waves, XL, ROUTE, EX and the
+    launch's nblk, block, lds_bytes"""
+    out = (ctypes.c_int32 * 18)()
+    n = list(N) + [0] * (3 - len(N))
+    rc = _L.kcpp_gemv_dec_plan(GEMV_ENTRY.index(entry), int(wtype), int(K), len(N), n[0], n[1], n[2], role[0], role[1], role[2],
+                               int(D), int(mode), int(pro), int(rows_per_wave), _gemv_flags(flags), int(route_wt),
+                               int(route_ne), out)
+    if rc:
+        return rc
+    d = dict(zip(_GEMV_PLAN_FIELDS, out))
+    d["kernel"] = GEMV_KERNEL[d["kernel"]]
+    return d
+
+
+def gemv_qkv_mixed_plan(K, N, flags=(), role=(0, 1, 2), D=0):
+    """what kcpp_gemv_rs_qkv_mixed launches (host only): its error code, or a dict of NIA, NIB, MC, EX, block, nblk,
+    lds_bytes"""
+    out = (ctypes.c_int32 * 8)()
+    rc = _L.kcpp_gemv_qkv_mixed_plan(int(K), N[0], N[1], N[2], role[0], role[1], role[2], int(D), _gemv_flags(flags), out)
+    return rc if rc else dict(zip(("rc", "NIA", "NIB", "MC", "EX", "block", "nblk", "lds_bytes"), out))
+
+
+def gemv_qkv_dual_plan(qtype, K, Na, Nb, flags_a=(), flags_b=(), Kb=None):
+    """what kcpp_gemv_qkv_dual launches (host only): its error code, or a dict of nblk, lds_bytes and the two halves'
+    a_nblk, a_lds_bytes, a_NI (the RS launch of q) and b_nblk, b_lds_bytes, b_IT (the unit launch of k|v in Q8_0)"""
+    out = (ctypes.c_int32 * 9)()
+    na, nb = (ctypes.c_int64 * 3)(*Na), (ctypes.c_int64 * 3)(*Nb)
+    rc = _L.kcpp_gemv_qkv_dual_plan(int(qtype), int(K), len(Na), na, _gemv_flags(flags_a), int(K if Kb is None else Kb), len(Nb),
+                                    nb, _gemv_flags(flags_b), out)
+    return rc if rc else dict(zip(("rc", "nblk", "lds_bytes", "a_nblk", "a_lds_bytes", "a_NI", "b_nblk", "b_lds_bytes", "b_IT"),
+                                  out))
 
 
 def pipeline_trace(n_stages, ubatch, T, n_past, steps):

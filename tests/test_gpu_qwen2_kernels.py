@@ -151,7 +151,7 @@ def test_fused_qkv_mixed_equals_unfused(env, E, H, HKV, D, pos):
 
 @pytest.mark.parametrize("ty", ["Q5_K_RS", "Q6_K_RS"])
 def test_fused_qkv_other_rs_types(env, ty):
-    """the single-type launch in the other two row-major layouts (pick_rs is generic over them) at K = 2048, the
+    """the single-type launch in the other two row-major layouts (one instance list serves all three) at K = 2048, the
     narrowest width Q6_K_RS exists at: (14, 2) heads of 128, position 37, the three bias / NeoX variants"""
     torch, K = env
     t = getattr(K, ty)
