@@ -438,6 +438,38 @@ void *kcpp_model_stream(kcpp_model *m);
 int kcpp_model_hidden_io(kcpp_model *m, void *buf, int64_t n_floats, int64_t offset, int dir);
 /* copy the last decode's logits [n_vocab] f32 to host memory (stage with the output head) */
 int kcpp_model_read_logits(kcpp_model *m, float *host);
+/* The device front end of SampleLogits (koboldcpp_amd/csrc/cand.h, cand.hip): applies the sparse logit edits -- ids set
+ * to LowestLogit of the raw logits, then (id, bias) added in list order, then (id, penalty) subtracted -- to a scratch
+ * copy of n f32 logits, finds the bucket cut of the reference's top_k(k) pre-filter (k > 128: 128 buckets of
+ * int(6.4 logit + 64)) and returns the candidates at or above the cut in ascending id with the bucket totals, from
+ * which the host's scatter and sorts give the same k candidates in the same order as from all n logits.  The logits
+ * are not modified.  nhave > cap (only the first cap survivors were written) and n_bad > 0 (some value's bucket is not
+ * defined on the host) are statuses in the header, not errors: the caller then samples from the full logits. */
+typedef struct kcpp_cand_edit { int32_t id; float v; } kcpp_cand_edit;
+typedef struct kcpp_cand_hdr {
+    float low;              /* LowestLogit(raw logits); 0 when n_set == 0 (no min pass runs) */
+    int32_t ib;             /* the cut bucket */
+    int32_t nhave;          /* candidates of bucket >= ib */
+    int32_t n_bad;          /* values that are not finite or whose |6.4 v + 64| >= 2^31 */
+    int32_t hist[128];      /* candidates per bucket */
+} kcpp_cand_hdr;
+/* on any device buffer of n <= 2^22 logits; ids_out / logits_out: cap entries (cap <= 16384), min(nhave, cap) written.
+ * Allocates its workspace per call and synchronises the stream: the unit the tests drive, not the serving path. */
+int kcpp_logit_candidates(const float *logits_dev, int n, int k, const int32_t *set_ids, int n_set, const kcpp_cand_edit *adds,
+                          int n_add, const kcpp_cand_edit *subs, int n_sub, kcpp_cand_hdr *hdr_out, int32_t *ids_out,
+                          float *logits_out, int cap, void *stream);
+/* the same on the last decode's logits of the stage with the output head, with buffers allocated at model creation:
+ * the edit lists go up from pinned staging on the stage's stream, the header and the first 8192 survivors come back
+ * in one transfer and one stream synchronisation (a second copy only when nhave > 8192) */
+int kcpp_model_candidates(kcpp_model *m, int k, const int32_t *set_ids, int n_set, const kcpp_cand_edit *adds, int n_add,
+                          const kcpp_cand_edit *subs, int n_sub, kcpp_cand_hdr *hdr_out, int32_t *ids_out, float *logits_out,
+                          int cap);
+/* the front end's launch plan for n logits (host only): out = {rc, slice (consecutive ids per workgroup), block, nblk} */
+int kcpp_cand_plan(int64_t n, int32_t out[4]);
+/* test hook: the CPU model of the device pass (kcand::cand_front_ref), same arguments and results, host memory only */
+int kcpp_cand_front_ref(const float *logits, int n, int k, const int32_t *set_ids, int n_set, const kcpp_cand_edit *adds,
+                        int n_add, const kcpp_cand_edit *subs, int n_sub, kcpp_cand_hdr *hdr_out, int32_t *ids_out,
+                        float *logits_out, int cap);
 /* wait for all work queued on the stage's stream */
 int kcpp_model_sync(kcpp_model *m);
 /* per-stage step without embedding/out: run layers on the hidden buffer for T tokens */
@@ -562,6 +594,27 @@ int kcpp_sampler_probe(const float *logits, int n_vocab, int n_ctx, const float 
                        int n_order, const int *ctx_toks, int n_ctx_toks, const int *last_n, int n_last,
                        const int *restarts, int n_restart_ints, unsigned seed, float *mu, int *out_ids, float *out_p,
                        int cap, int *out_n);
+/* the same through the sampling front end's host side (the CPU model of the device pass, then the host tail), on raw
+ * logits plus the edits that precede the chain: set_ids set to the lowest logit, (add_ids, add_v) added in order,
+ * (sub_ids, sub_v) subtracted.  *status_out: 0 through the front end; 1 / 2 / 3 it fell back to the full chain (n_bad,
+ * more survivors than the capacity, bucket mismatch).  Host only */
+int kcpp_sampler_probe_front(const float *logits, int n_vocab, int n_ctx, const float *fp, const int *ip, const int *order,
+                             int n_order, const int *ctx_toks, int n_ctx_toks, const int *last_n, int n_last,
+                             const int *restarts, int n_restart_ints, unsigned seed, float *mu, int *out_ids, float *out_p,
+                             int cap, int *out_n, const int *set_ids, int n_set, const int *add_ids, const float *add_v,
+                             int n_add, const int *sub_ids, const float *sub_v, int n_sub, int *status_out);
+/* generate()'s sampled tokens start from the device's candidates (kcpp_model_candidates) instead of a read of every
+ * logit: on 1 / off 0 for the calls that follow, -1 = the environment's answer (KCPP_SAMPLE_DEV, read per call; unset:
+ * on).  The drawn tokens are the same either way. */
+void kcpp_expose_set_sample_front(int on);
+/* out = {tokens sampled through the front end, fallbacks to the full read for n_bad, for nhave > capacity, for a host /
+ * device bucket mismatch} since the last call; reading resets them */
+void kcpp_expose_sample_front_stats(int64_t out[4]);
+/* test hook: SampleLogits' process-lifetime mirostat_mu (the reference's function-static); set != 0 assigns value
+ * first; returns the current mu.  Lets one process run the same mirostat request twice from the same state */
+float kcpp_expose_mirostat_mu(int set, float value);
+/* the token ids the last generate() sampled, in order (up to cap written); returns their number */
+int kcpp_expose_last_tokens(int *out, int cap);
 
 #ifdef __cplusplus
 }

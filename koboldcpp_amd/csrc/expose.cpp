@@ -14,6 +14,8 @@
 // DRY, rep_pen, top-k/a/p, min-p, tfs, typical, temperature / dynatemp / smoothing, mirostat, XTC) over
 // the user's sampler_order and a seeded mt19937; when that chain reduces to argmax (greedy, no biases /
 // penalties / bans) the token comes from the on-device argmax instead of a logits copy.
+// A sampled token starts from the device's candidates (cand.h: the logit edits and the top-5000 pre-filter's bucket
+// cut run on the GPU, sample_front) instead of a read of every logit; the sorts and everything after stay here.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
@@ -35,6 +37,7 @@
 #include "../../include/kcpp_expose.h"
 #include "../../include/kcpp_mi355x.h"
 #include "../../include/kcpp_synth.h"
+#include "cand.h"
 #include "gguf.h"
 #include "kcpp_internal.h"
 #include "sampler.h"
@@ -96,6 +99,11 @@ struct Engine {
     // the last stage's argmax_dev holds the greedy token of the current logits AND stage 0's token input holds the
     // same token: true after a single-token step (its graph ends in the argmax) once the token is home
     bool dev_tok = false;
+    // sampling front end (sample_front): edit lists and results of one token, kept for their capacity
+    std::vector<int32_t> f_set, f_ids;
+    std::vector<kcpp_cand_edit> f_add, f_sub;
+    std::vector<float> f_vals;
+    std::vector<ksamp::TokData> f_cand;
     ~Engine() {
         for (size_t s = 0; s < stages.size(); ++s) {
             hipSetDevice(devs[s]);
@@ -119,6 +127,12 @@ int g_last_count = 0, g_last_seed = 0, g_total_gens = 0;
 float g_mirostat_mu = 0.0f;
 int g_last_stop = KCPP_STOP_INVALID;
 std::vector<int> g_count_ids;
+// the device front end of sampled tokens (sample_front): on unless KCPP_SAMPLE_DEV=0 (read per generate() call) or
+// kcpp_expose_set_sample_front says otherwise (-1: the environment's answer)
+constexpr bool kSampleFrontDefault = true;
+int g_front_override = -1;
+int64_t g_front_stats[4] = {0, 0, 0, 0};    // tokens through the front end; fallbacks: n_bad, overflow, mismatch
+std::vector<int> g_last_tokens;             // the token ids of the last generate() (kcpp_expose_last_tokens)
 
 const char *tname(int il, int j) {
     static const char *n[9] = {"attn_norm", "attn_q", "attn_k", "attn_v", "attn_output", "ffn_norm", "ffn_gate", "ffn_up", "ffn_down"};
@@ -462,6 +476,7 @@ struct SamplerSetup {
     int delay = 0;                         // delayed_generated_tokens_limit: tokens held back before streaming
     int n_ctx = 0;
     bool suppress_eos = false;
+    bool front = false;                    // sampled tokens start from the device's candidates (sample_front)
 };
 
 std::string lower(std::string s) {
@@ -554,6 +569,8 @@ SamplerSetup make_sampler(const Engine &e, const generation_inputs &in, int n_ct
                 if (w.find(b) != std::string::npos) { S.banned.push_back(v); break; }
         }
     S.suppress_eos = !in.allow_eos_token && !in.bypass_eos_token;
+    const char *sd = getenv("KCPP_SAMPLE_DEV");
+    S.front = g_front_override >= 0 ? g_front_override != 0 : (sd && sd[0] ? atoi(sd) != 0 : kSampleFrontDefault);
     return S;
 }
 
@@ -569,6 +586,47 @@ bool chain_is_argmax(const SamplerSetup &S) {
     bool has_temp = false, has_topk = false;
     for (int s : P.order) { has_temp |= s == ksamp::S_TEMP; has_topk |= s == ksamp::S_TOP_K; }
     return (has_topk && (int)P.top_k == 1) || (has_temp && P.temp <= 0 && P.dynatemp_range <= 0);
+}
+
+// A sampled token from the device's candidates instead of all n_vocab logits (cand.h): the edits that precede
+// SampleLogits' top_k(5000) -- EOS / EOT, bans and antislop set to the lowest logit, the logit biases, the DRY
+// penalties -- go to the device as lists, the candidates at or above the pre-filter's bucket cut come back in id order,
+// and the host's own scatter and sorts (kcand::top_k_from_survivors) leave the 5000 candidates the full chain would
+// have; the rest of the chain is unchanged.  1: *tok is the token; 0: fall back to the full read (a value whose bucket
+// the host does not define, more survivors than the capacity, or the host's buckets disagreeing with the device's;
+// nothing has been drawn from rng); < 0: a device error.
+int sample_front(Engine &e, const SamplerSetup &S, const std::vector<int> &last_n, std::mt19937 &rng, float *mu,
+                 const std::vector<int> *slop, int *tok) {
+    const int nv = e.hp.n_vocab, eos = e.tok.eos(), eot = e.tok.eot();
+    e.f_set.clear(), e.f_add.clear(), e.f_sub.clear();
+    if (S.suppress_eos && eos >= 0 && eos < nv) e.f_set.push_back(eos);
+    if (S.suppress_eos && eot >= 0 && eot < nv) e.f_set.push_back(eot);
+    e.f_set.insert(e.f_set.end(), S.banned.begin(), S.banned.end());
+    if (slop)
+        for (int b : *slop)
+            if (b >= 0 && b < nv) e.f_set.push_back(b);
+    for (const ksamp::LogitBias &b : S.biases) e.f_add.push_back(kcpp_cand_edit{b.token_id, b.bias});
+    const ksamp::Params &P = S.P;
+    for (const ksamp::DryPenalty &d : ksamp::dry_penalties(S.n_ctx, P.dry_penalty_last_n, P.dry_multiplier, P.dry_base,
+                                                           P.dry_allowed_length, S.restarts, e.ctx))
+        e.f_sub.push_back(kcpp_cand_edit{d.id, d.penalty});
+    e.f_ids.resize(kcand::CAND_CAP), e.f_vals.resize(kcand::CAND_CAP);
+    kcpp_cand_hdr hdr;
+    if (kcpp_model_candidates(e.stages.back(), kcand::CAND_K, e.f_set.data(), (int)e.f_set.size(), e.f_add.data(),
+                              (int)e.f_add.size(), e.f_sub.data(), (int)e.f_sub.size(), &hdr, e.f_ids.data(), e.f_vals.data(),
+                              kcand::CAND_CAP))
+        return -1;
+    if (hdr.n_bad > 0) { ++g_front_stats[1]; return 0; }
+    if (hdr.nhave > kcand::CAND_CAP) { ++g_front_stats[2]; return 0; }
+    kcand::Hdr h;
+    memcpy(&h, &hdr, sizeof(h));
+    if (!kcand::top_k_from_survivors(h, e.f_ids.data(), e.f_vals.data(), hdr.nhave, nv, kcand::CAND_K, e.f_cand)) {
+        ++g_front_stats[3];
+        return 0;
+    }
+    ++g_front_stats[0];
+    *tok = ksamp::sample_candidates(e.f_cand, S.n_ctx, nv, P, last_n, rng, mu);
+    return 1;
 }
 
 // one sampled token from the last stage's logits (gpttype_adapter.cpp:3182-3232); < 0 on a device error.
@@ -587,6 +645,12 @@ int sample(Engine &e, const SamplerSetup &S, const std::vector<int> &last_n, std
             *on_dev = true;
             return t;
         }
+    }
+    // at or below 5000 every candidate survives: nothing to gain
+    if (S.front && e.hp.n_vocab > kcand::CAND_K && e.hp.n_vocab <= kcand::CAND_MAX_N) {
+        int t = 0;
+        const int r = sample_front(e, S, last_n, rng, mu, slop, &t);
+        if (r) return r < 0 ? -1 : t;
     }
     e.logits.resize(e.hp.n_vocab);
     if (kcpp_model_read_logits(last, e.logits.data())) return -1;
@@ -671,6 +735,24 @@ int purge_missing_tokens(Engine &e, std::vector<int> &cur, const std::vector<int
     cur.resize(cur.size() - diff);
     fprintf(stderr, "[kcpp] Context Shifting: Erased %d tokens at position %d\n", diff, trimstart + 1);
     return diff;
+}
+
+// the sampler test hooks' parameter arrays (kcpp_sampler_probe's comment) as Params and restart sequences
+bool probe_params(const float *fp, const int *ip, const int *order, int n_order, const int *restarts, int n_restart_ints,
+                  ksamp::Params &P, ksamp::RestartSeqs &rs) {
+    P.top_k = fp[0]; P.top_a = fp[1]; P.top_p = fp[2]; P.min_p = fp[3]; P.typical_p = fp[4]; P.tfs = fp[5]; P.temp = fp[6];
+    P.rep_pen = fp[7]; P.rep_pen_slope = fp[8]; P.presence_penalty = fp[9]; P.mirostat_tau = fp[10]; P.mirostat_eta = fp[11];
+    P.dry_multiplier = fp[12]; P.dry_base = fp[13]; P.xtc_threshold = fp[14]; P.xtc_probability = fp[15];
+    P.dynatemp_range = fp[16]; P.dynatemp_exponent = fp[17]; P.smoothing_factor = fp[18];
+    P.rep_pen_range = ip[0]; P.mirostat = ip[1]; P.dry_allowed_length = ip[2]; P.dry_penalty_last_n = ip[3];
+    for (int i = 0; i < n_order; ++i) P.order.push_back(order[i]);
+    for (int i = 0; i + 1 < n_restart_ints;) {
+        const int head = restarts[i], len = restarts[i + 1];
+        if (len < 0 || i + 2 + len > n_restart_ints) return false;
+        rs.emplace(head, std::vector<int>(restarts + i + 2, restarts + i + 2 + len));
+        i += 2 + len;
+    }
+    return true;
 }
 
 }  // namespace
@@ -1006,6 +1088,7 @@ generation_outputs generate(const generation_inputs in) {
             if (p != std::string::npos) { g_concat.resize(p); hit = true; break; }
         }
     };
+    g_last_tokens.clear();
     int n_gen = 0, stop = KCPP_STOP_OUT_OF_TOKENS;
     double tm_sample = 0, tm_step = 0;     // host time in sample() / in the step's enqueue (KCPP_GEN_TIMING diagnostics)
     for (; n_gen < max_len; ++n_gen) {
@@ -1016,6 +1099,7 @@ generation_outputs generate(const generation_inputs in) {
         const int t = sample(*e, S, last_n, rng, &g_mirostat_mu, sb == slop.end() ? nullptr : &sb->second, &on_dev);
         tm_sample += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts0).count();
         if (t < 0) { fprintf(stderr, "[kcpp] generate: sampling failed: %s\n", kcpp_last_error()); break; }
+        g_last_tokens.push_back(t);
         if (!last_n.empty()) last_n.erase(last_n.begin());     // (:3238: an antislop rewind may have emptied it)
         last_n.push_back(t);
         const bool eos_tok = t == e->tok.eos() || (t == e->tok.eot() && t != -1);
@@ -1292,19 +1376,8 @@ int kcpp_sampler_probe(const float *logits, int n_vocab, int n_ctx, const float 
                        int cap, int *out_n) {
     if (!logits || n_vocab <= 0 || !fp || !ip) return -1;
     ksamp::Params P;
-    P.top_k = fp[0]; P.top_a = fp[1]; P.top_p = fp[2]; P.min_p = fp[3]; P.typical_p = fp[4]; P.tfs = fp[5]; P.temp = fp[6];
-    P.rep_pen = fp[7]; P.rep_pen_slope = fp[8]; P.presence_penalty = fp[9]; P.mirostat_tau = fp[10]; P.mirostat_eta = fp[11];
-    P.dry_multiplier = fp[12]; P.dry_base = fp[13]; P.xtc_threshold = fp[14]; P.xtc_probability = fp[15];
-    P.dynatemp_range = fp[16]; P.dynatemp_exponent = fp[17]; P.smoothing_factor = fp[18];
-    P.rep_pen_range = ip[0]; P.mirostat = ip[1]; P.dry_allowed_length = ip[2]; P.dry_penalty_last_n = ip[3];
-    for (int i = 0; i < n_order; ++i) P.order.push_back(order[i]);
     ksamp::RestartSeqs rs;
-    for (int i = 0; i + 1 < n_restart_ints;) {
-        const int head = restarts[i], len = restarts[i + 1];
-        if (len < 0 || i + 2 + len > n_restart_ints) return -1;
-        rs.emplace(head, std::vector<int>(restarts + i + 2, restarts + i + 2 + len));
-        i += 2 + len;
-    }
+    if (!probe_params(fp, ip, order, n_order, restarts, n_restart_ints, P, rs)) return -1;
     const std::vector<int> ctxv(ctx_toks, ctx_toks + n_ctx_toks), lastv(last_n, last_n + n_last);
     std::mt19937 rng(seed);
     std::vector<ksamp::TokData> cand;
@@ -1329,6 +1402,93 @@ int kcpp_sampler_probe(const float *logits, int n_vocab, int n_ctx, const float 
     for (int i = 0; i < n; ++i) { out_ids[i] = c.data[i].id; out_p[i] = c.data[i].p; }
     if (out_n) *out_n = (int)c.size;
     return tok;
+}
+
+// test hook (tests/test_sample_front.py): kcpp_sampler_probe through the sampling front end's host side, no device:
+// kcand::cand_front_ref (the CPU model of the device pass) on the raw logits and the edit lists -- set_ids set to the
+// lowest logit, (add_ids, add_v) added in order, (sub_ids, sub_v) then the DRY penalties subtracted --
+// kcand::top_k_from_survivors and the rest of the chain.  *status_out: 0 through the front end; 1 n_bad, 2 more
+// survivors than the capacity, 3 bucket mismatch: the chain then ran from the edited full logits, as generate() falls
+// back.  Same outputs as kcpp_sampler_probe on logits that already carry the edits.
+int kcpp_sampler_probe_front(const float *logits, int n_vocab, int n_ctx, const float *fp, const int *ip, const int *order,
+                             int n_order, const int *ctx_toks, int n_ctx_toks, const int *last_n, int n_last,
+                             const int *restarts, int n_restart_ints, unsigned seed, float *mu, int *out_ids, float *out_p,
+                             int cap, int *out_n, const int *set_ids, int n_set, const int *add_ids, const float *add_v,
+                             int n_add, const int *sub_ids, const float *sub_v, int n_sub, int *status_out) {
+    if (!logits || n_vocab <= 0 || !fp || !ip || n_set < 0 || n_add < 0 || n_sub < 0) return -1;
+    ksamp::Params P;
+    ksamp::RestartSeqs rs;
+    if (!probe_params(fp, ip, order, n_order, restarts, n_restart_ints, P, rs)) return -1;
+    const std::vector<int> ctxv(ctx_toks, ctx_toks + n_ctx_toks), lastv(last_n, last_n + n_last);
+    const std::vector<int32_t> setv(set_ids, set_ids + n_set);
+    std::vector<kcand::Edit> adds, subs;
+    for (int i = 0; i < n_add; ++i) adds.push_back(kcand::Edit{add_ids[i], add_v[i]});
+    for (int i = 0; i < n_sub; ++i) subs.push_back(kcand::Edit{sub_ids[i], sub_v[i]});
+    const size_t n_sub_given = subs.size();
+    for (const ksamp::DryPenalty &d : ksamp::dry_penalties(n_ctx, P.dry_penalty_last_n, P.dry_multiplier, P.dry_base,
+                                                           P.dry_allowed_length, rs, ctxv))
+        subs.push_back(kcand::Edit{d.id, d.penalty});
+    kcand::Hdr hdr;
+    std::vector<int32_t> ids;
+    std::vector<float> vals;
+    if (kcand::cand_front_ref(logits, n_vocab, kcand::CAND_K, setv.data(), n_set, adds.data(), n_add, subs.data(),
+                              (int)subs.size(), &hdr, ids, vals, kcand::CAND_CAP))
+        return -1;
+    std::vector<ksamp::TokData> cand;
+    int status = hdr.n_bad > 0 ? 1 : (hdr.nhave > kcand::CAND_CAP ? 2 : 0);
+    if (!status && !kcand::top_k_from_survivors(hdr, ids.data(), vals.data(), (int)ids.size(), n_vocab, kcand::CAND_K, cand))
+        status = 3;
+    if (status_out) *status_out = status;
+    const bool miro = P.mirostat == 1 || P.mirostat == 2;
+    std::mt19937 rng(seed);
+    float mu2 = *mu;
+    int tok;
+    ksamp::Cands c{nullptr, 0, false};
+    std::vector<float> l;
+    if (status) {                          // as sample()'s full path: the edits on a host copy, DRY inside the chain
+        l.assign(logits, logits + n_vocab);
+        const float low = ksamp::lowest_logit(logits, (size_t)n_vocab);
+        for (int id : setv) l[id] = low;
+        for (const kcand::Edit &a : adds) l[a.id] += a.v;
+        for (size_t i = 0; i < n_sub_given; ++i) l[subs[i].id] -= subs[i].v;
+    }
+    if (miro) {
+        tok = status ? ksamp::sample_logits(l.data(), n_ctx, n_vocab, P, {}, rs, ctxv, lastv, rng, &mu2)
+                     : ksamp::sample_candidates(cand, n_ctx, n_vocab, P, lastv, rng, &mu2);
+        *mu = mu2;
+    } else {
+        c = status ? ksamp::apply_chain(cand, l.data(), n_ctx, n_vocab, P, {}, rs, ctxv, lastv, rng, false)
+                   : ksamp::apply_order(ksamp::Cands{cand.data(), cand.size(), true}, n_ctx, P, lastv, rng, false);
+        std::vector<ksamp::TokData> keep(c.data, c.data + c.size);
+        ksamp::Cands ck{keep.data(), keep.size(), c.sorted};
+        tok = ksamp::draw(&ck, rng);
+        ksamp::softmax(&c);             // the probabilities the draw used
+    }
+    const int n = (int)std::min<size_t>(c.size, (size_t)std::max(cap, 0));
+    for (int i = 0; i < n; ++i) { out_ids[i] = c.data[i].id; out_p[i] = c.data[i].p; }
+    if (out_n) *out_n = (int)c.size;
+    return tok;
+}
+
+// the sampling front end's switch for the generate() calls that follow: 1 on, 0 off, -1 the environment's answer
+// (KCPP_SAMPLE_DEV, read per call; unset: on)
+void kcpp_expose_set_sample_front(int on) { g_front_override = on < 0 ? -1 : (on != 0); }
+// out = {tokens sampled through the front end, fallbacks for n_bad, for more survivors than the capacity, for a bucket
+// mismatch} since the last call; reading resets them
+void kcpp_expose_sample_front_stats(int64_t out[4]) {
+    for (int i = 0; i < 4; ++i) { out[i] = g_front_stats[i]; g_front_stats[i] = 0; }
+}
+// SampleLogits' mirostat_mu lives as long as the process (the reference's function-static): a test that runs one
+// mirostat request twice sets it back in between.  set != 0: mu = value; returns the current mu
+float kcpp_expose_mirostat_mu(int set, float value) {
+    if (set) g_mirostat_mu = value;
+    return g_mirostat_mu;
+}
+// the token ids the last generate() sampled, in order (up to cap written); returns how many there are
+int kcpp_expose_last_tokens(int *out, int cap) {
+    const int n = (int)g_last_tokens.size();
+    for (int i = 0; i < std::min(n, std::max(cap, 0)); ++i) out[i] = g_last_tokens[i];
+    return n;
 }
 
 const char *new_token(int idx) {

@@ -27,6 +27,7 @@
 
 #include "../../include/kcpp_mi355x.h"
 #include "../../include/kcpp_synth.h"
+#include "cand.h"
 #include "fa_plan.h"
 #include "kcpp_internal.h"
 
@@ -99,6 +100,10 @@ struct KLayer {
     float *bq = nullptr, *bk = nullptr, *bv = nullptr;   // q / k / v projection biases (Qwen2), device f32; null: none
 };
 
+struct CandCtx;                          // the sampling front end's buffers (below, with its entries)
+static CandCtx *cand_create(int n, int cap, int64_t max_ops);
+static void cand_free(CandCtx *c);
+
 struct kcpp_model {
     kcpp_hparams hp;
     std::vector<int> types;
@@ -145,6 +150,7 @@ struct kcpp_model {
     int lag_k = 0;                   // lagged steps enqueued since the last drain
     int pos_val = -1;                // the value pos_dev holds once the enqueued work has run (-1: unknown)
     float *logits_pin = nullptr;
+    CandCtx *cand = nullptr;         // output stage: kcpp_model_candidates' workspace, staging and result buffers
     bool use_graphs = true;
     bool fused_decode = true;        // single-token path through gemv_dec (norm/rope/KV fused)
     bool q81 = false;                // Q4_1 / Q5_1 weights (Q8_1 activations): decode on the per-op path
@@ -559,6 +565,11 @@ extern "C" kcpp_model *kcpp_model_create(const kcpp_hparams *hp, const int *type
         if (hipMalloc(&m->logits, (size_t)hp->n_vocab * 4) != hipSuccess) return fail("logits alloc");
         if (hipHostMalloc((void **)&m->logits_pin, (size_t)hp->n_vocab * 4, hipHostMallocDefault) != hipSuccess)
             return fail("logits pin");
+        if (hp->n_vocab <= kcand::CAND_MAX_N &&
+            !(m->cand = cand_create(hp->n_vocab, kcand::CAND_CAP, 2 * (int64_t)hp->n_vocab + 64))) {
+            kcpp_model_free(m);          // g_err names the allocation
+            return nullptr;
+        }
     }
     std::vector<float> tab((size_t)hp->n_ctx * D);
     kcpp_rope_table(tab.data(), hp->n_ctx, (int)D, hp->rope_base, hp->rope_freq_scale, nullptr, 0.0f, 1.0f, 32.0f, 1.0f,
@@ -593,6 +604,7 @@ extern "C" void kcpp_model_free(kcpp_model *m) {
     if (m->pin) hipHostFree(m->pin);
     for (hipEvent_t &ev : m->ev_tok) if (ev) hipEventDestroy(ev);
     if (m->logits_pin) hipHostFree(m->logits_pin);
+    cand_free(m->cand);
     if (m->stream) hipStreamDestroy(m->stream);
     if (m->side) hipStreamDestroy(m->side);
     if (m->ev_fork) hipEventDestroy(m->ev_fork);
@@ -717,6 +729,134 @@ extern "C" int kcpp_model_read_logits(kcpp_model *m, float *host) {
     memcpy(host, m->logits_pin, (size_t)m->hp.n_vocab * 4);
     return 0;
 }
+
+// ---- the device front end of SampleLogits (cand.h, cand.hip)
+struct CandCtx {
+    int n_max = 0, cap = 0;
+    int64_t max_ops = 0;
+    kcand::WsLayout w{};
+    uint8_t *ws = nullptr;               // device workspace (kcand::ws_layout)
+    kcand::Op *ops_pin = nullptr;        // pinned staging of the edit program
+    uint8_t *out_pin = nullptr;          // pinned: Hdr, then cap Pairs
+    std::vector<uint64_t> keys;
+};
+static void cand_free(CandCtx *c) {
+    if (!c) return;
+    if (c->ws) hipFree(c->ws);
+    if (c->ops_pin) hipHostFree(c->ops_pin);
+    if (c->out_pin) hipHostFree(c->out_pin);
+    delete c;
+}
+static CandCtx *cand_create(int n, int cap, int64_t max_ops) {
+    CandCtx *c = new CandCtx;
+    c->n_max = n, c->cap = cap, c->max_ops = max_ops;
+    c->w = kcand::ws_layout(n, max_ops, cap);
+    const char *what = "workspace";
+    hipError_t e = hipMalloc((void **)&c->ws, c->w.bytes);
+    if (e == hipSuccess) {
+        what = "edit staging";
+        e = hipHostMalloc((void **)&c->ops_pin, (size_t)std::max<int64_t>(1, max_ops) * sizeof(kcand::Op), hipHostMallocDefault);
+    }
+    if (e == hipSuccess) {
+        what = "result staging";
+        e = hipHostMalloc((void **)&c->out_pin, sizeof(kcand::Hdr) + (size_t)cap * sizeof(kcand::Pair), hipHostMallocDefault);
+    }
+    if (e != hipSuccess) {
+        g_err = std::string("candidates: ") + what + " alloc: " + hipGetErrorString(e);
+        cand_free(c);
+        return nullptr;
+    }
+    return c;
+}
+static_assert(sizeof(kcpp_cand_hdr) == sizeof(kcand::Hdr) && sizeof(kcpp_cand_edit) == sizeof(kcand::Edit), "cand ABI");
+// edits up, the passes, results back: one stream synchronisation while nhave <= CAND_FIRST
+static int cand_run(CandCtx *c, const float *logits_dev, int n, int k, const int32_t *set_ids, int n_set,
+                    const kcpp_cand_edit *adds, int n_add, const kcpp_cand_edit *subs, int n_sub, kcpp_cand_hdr *hdr_out,
+                    int32_t *ids_out, float *logits_out, int cap, hipStream_t s) {
+    kcand::Plan p;
+    if (!c || !logits_dev || !hdr_out || n > c->n_max || kcand::plan(n, &p)) { g_err = "candidates: n out of range"; return -2; }
+    if (cap < 0 || cap > c->cap || (cap > 0 && (!ids_out || !logits_out))) { g_err = "candidates: bad capacity"; return -2; }
+    if (n_set < 0 || n_add < 0 || n_sub < 0 || (n_set && !set_ids) || (n_add && !adds) || (n_sub && !subs)) {
+        g_err = "candidates: bad edit lists";
+        return -2;
+    }
+    k = std::min(std::max(k, 1), n);
+    const int64_t nops = kcand::build_ops(n, set_ids, n_set, (const kcand::Edit *)adds, n_add, (const kcand::Edit *)subs, n_sub,
+                                          c->keys, c->ops_pin, c->max_ops);
+    if (nops < 0) { g_err = nops == -1 ? "candidates: edit id outside the vocabulary" : "candidates: too many edits"; return -2; }
+    uint8_t *ws = c->ws;
+    if (nops > 0) RT_CHECK(hipMemcpyAsync(ws + c->w.ops, c->ops_pin, (size_t)nops * sizeof(kcand::Op), hipMemcpyHostToDevice, s));
+    kcand::Args a{};
+    a.logits = logits_dev, a.n = n, a.k = k, a.cap = cap;
+    a.ops = (const kcand::Op *)(ws + c->w.ops), a.nops = (int)nops, a.n_set = n_set;
+    a.scratch = (float *)(ws + c->w.scratch), a.minpart = (float *)(ws + c->w.minpart), a.low = (float *)(ws + c->w.low);
+    a.hist = (int32_t *)(ws + c->w.hist), a.bad = (int32_t *)(ws + c->w.bad), a.off = (int32_t *)(ws + c->w.off);
+    a.out = ws + c->w.out;
+    if (int rc = kcpp_cand_launch(p, a, s)) { g_err = "candidates: launch failed"; return rc; }
+    const int first = std::min(cap, kcand::CAND_FIRST);
+    RT_CHECK(hipMemcpyAsync(c->out_pin, a.out, sizeof(kcand::Hdr) + (size_t)first * sizeof(kcand::Pair), hipMemcpyDeviceToHost, s));
+    RT_CHECK(hipStreamSynchronize(s));
+    memcpy(hdr_out, c->out_pin, sizeof(kcand::Hdr));
+    const int have = std::max(0, std::min(hdr_out->nhave, cap));
+    if (have > first) {
+        const size_t at = sizeof(kcand::Hdr) + (size_t)first * sizeof(kcand::Pair);
+        RT_CHECK(hipMemcpyAsync(c->out_pin + at, (const uint8_t *)a.out + at, (size_t)(have - first) * sizeof(kcand::Pair),
+                                hipMemcpyDeviceToHost, s));
+        RT_CHECK(hipStreamSynchronize(s));
+    }
+    const kcand::Pair *pr = (const kcand::Pair *)(c->out_pin + sizeof(kcand::Hdr));
+    for (int i = 0; i < have; ++i) { ids_out[i] = pr[i].id; logits_out[i] = pr[i].v; }
+    return 0;
+}
+
+extern "C" int kcpp_logit_candidates(const float *logits_dev, int n, int k, const int32_t *set_ids, int n_set,
+                                     const kcpp_cand_edit *adds, int n_add, const kcpp_cand_edit *subs, int n_sub,
+                                     kcpp_cand_hdr *hdr_out, int32_t *ids_out, float *logits_out, int cap, void *stream) {
+    kcand::Plan p;
+    if (kcand::plan(n, &p) || cap < 0 || cap > kcand::CAND_CAP || n_set < 0 || n_add < 0 || n_sub < 0) {
+        g_err = "candidates: n, cap or list length out of range";
+        return -2;
+    }
+    CandCtx *c = cand_create(n, cap, (int64_t)n_set + n_add + n_sub);
+    if (!c) return -1;
+    const int rc = cand_run(c, logits_dev, n, k, set_ids, n_set, adds, n_add, subs, n_sub, hdr_out, ids_out, logits_out, cap,
+                            (hipStream_t)stream);
+    if (rc) (void)hipStreamSynchronize((hipStream_t)stream);       // nothing may still read the workspace
+    cand_free(c);
+    return rc;
+}
+extern "C" int kcpp_model_candidates(kcpp_model *m, int k, const int32_t *set_ids, int n_set, const kcpp_cand_edit *adds,
+                                     int n_add, const kcpp_cand_edit *subs, int n_sub, kcpp_cand_hdr *hdr_out, int32_t *ids_out,
+                                     float *logits_out, int cap) {
+    if (!m || !m->has_output || !m->cand) { g_err = "candidates: stage has no output head"; return -2; }
+    RT_CHECK(hipSetDevice(m->device));
+    return cand_run(m->cand, m->logits, m->hp.n_vocab, k, set_ids, n_set, adds, n_add, subs, n_sub, hdr_out, ids_out,
+                    logits_out, cap, m->stream);
+}
+extern "C" int kcpp_cand_plan(int64_t n, int32_t out[4]) {
+    kcand::Plan p;
+    const int rc = kcand::plan(n, &p);
+    out[0] = p.rc, out[1] = p.slice, out[2] = p.block, out[3] = p.nblk;
+    return rc;
+}
+extern "C" int kcpp_cand_front_ref(const float *logits, int n, int k, const int32_t *set_ids, int n_set,
+                                   const kcpp_cand_edit *adds, int n_add, const kcpp_cand_edit *subs, int n_sub,
+                                   kcpp_cand_hdr *hdr_out, int32_t *ids_out, float *logits_out, int cap) {
+    if (!logits || !hdr_out || cap < 0 || (cap > 0 && (!ids_out || !logits_out)) || n_set < 0 || n_add < 0 || n_sub < 0) {
+        g_err = "cand_front_ref: bad arguments";
+        return -2;
+    }
+    std::vector<int32_t> ids;
+    std::vector<float> vals;
+    kcand::Hdr h;
+    const int rc = kcand::cand_front_ref(logits, n, k, set_ids, n_set, (const kcand::Edit *)adds, n_add, (const kcand::Edit *)subs,
+                                         n_sub, &h, ids, vals, cap);
+    if (rc) { g_err = "cand_front_ref: n or an edit id out of range"; return -2; }
+    memcpy(hdr_out, &h, sizeof(h));
+    for (size_t i = 0; i < ids.size(); ++i) { ids_out[i] = ids[i]; logits_out[i] = vals[i]; }
+    return 0;
+}
+
 extern "C" int64_t kcpp_model_weight_bytes(kcpp_model *m) { return m->weight_bytes; }
 extern "C" int kcpp_model_set_graphs(kcpp_model *m, int enable) {
     m->use_graphs = enable != 0 && m->lanes.empty();   // split buffers disable graphs (ggml-cuda.cu graph_compute)

@@ -192,12 +192,16 @@ inline void xtc(Cands *c, float threshold, float probability, std::mt19937 &rng)
 }
 
 // sample_dry, gpttype_adapter.cpp:744-948 (restart-sequence limit, reverse Z-algorithm, per-token max repeat)
-inline void dry(int n_ctx, int range, float mult, float base, int allowed, const RestartSeqs &restarts,
-                const std::vector<int> &ctx_tokens, Cands *c) {
-    if (mult <= 0.0f || base <= 0.0f) return;
+// The penalties depend on the context tokens only, never on the logits: dry_penalties returns them as (id, penalty) in
+// the order the reference subtracts them, dry applies them.
+struct DryPenalty { int id; float penalty; };
+inline std::vector<DryPenalty> dry_penalties(int n_ctx, int range, float mult, float base, int allowed,
+                                             const RestartSeqs &restarts, const std::vector<int> &ctx_tokens) {
+    std::vector<DryPenalty> out;
+    if (mult <= 0.0f || base <= 0.0f) return out;
     if (range <= 0 || range > n_ctx) range = n_ctx;
     const int nrep = std::min(std::min((int)ctx_tokens.size(), range), n_ctx);
-    if (nrep <= allowed) return;
+    if (nrep <= allowed) return out;
     const int *last_tokens = ctx_tokens.data() + ctx_tokens.size() - nrep;
     std::vector<int> rc(nrep, 0);
     int rep_limit = nrep;
@@ -217,7 +221,7 @@ inline void dry(int n_ctx, int range, float mult, float base, int allowed, const
         }
         if (longest >= 0) { rep_limit = (int)i - longest; break; }
     }
-    if (rep_limit <= allowed) return;
+    if (rep_limit <= allowed) return out;
     {
         const int last = nrep - 1;
         int rt = 0, lt = 0;
@@ -253,15 +257,19 @@ inline void dry(int n_ctx, int range, float mult, float base, int allowed, const
     const float FLOAT_MAX_LOG = 88.7228391f;
     int max_exp = 0;
     if (base > 1.000001f) max_exp = (int)(FLOAT_MAX_LOG / std::log(base));
-    size_t count = 0;
     for (const auto &kv : maxrep) {
         int e = kv.second - allowed;
         if (max_exp > 0 && e > max_exp) e = max_exp;
         const float penalty = mult * pow(base, e);                // pow(float, int) is double, as in the reference
-        c->data[kv.first].logit -= penalty;                        // candidates are still id-indexed here
-        ++count;
+        out.push_back(DryPenalty{kv.first, penalty});
     }
-    if (count > 0) c->sorted = false;
+    return out;
+}
+inline void dry(int n_ctx, int range, float mult, float base, int allowed, const RestartSeqs &restarts,
+                const std::vector<int> &ctx_tokens, Cands *c) {
+    const std::vector<DryPenalty> pen = dry_penalties(n_ctx, range, mult, base, allowed, restarts, ctx_tokens);
+    for (const DryPenalty &d : pen) c->data[d.id].logit -= d.penalty;     // candidates are still id-indexed here
+    if (!pen.empty()) c->sorted = false;
 }
 
 // sample_rep_pen, gpttype_adapter.cpp:950-1007 (near half at full penalty, far half at the sloped penalty)
@@ -414,24 +422,11 @@ inline void temperature(Cands *c, float temp, float smoothing) {
     if (greedy) top_k(c, 1);
 }
 
-// SampleLogits, gpttype_adapter.cpp:1338-1434 (grammar omitted).  `logits` already carries the EOS /
-// banned-token suppression the caller applies (gpttype_adapter.cpp:3200-3224).  mirostat_mu is the
-// function-static of the reference (initialised once per process to 2 * tau).
 struct LogitBias { int token_id; float bias; };
 
-// the candidate chain of SampleLogits up to (not including) the final draw: biases, DRY, top-5000, then the
-// user's sampler order and XTC.  `cand` holds the candidates; returns the array view.  (mirostat: not here)
-inline Cands apply_chain(std::vector<TokData> &cand, const float *logits, int n_ctx, int n_vocab, const Params &P,
-                         const std::vector<LogitBias> &biases, const RestartSeqs &restarts,
-                         const std::vector<int> &ctx_tokens, const std::vector<int> &last_n, std::mt19937 &rng,
+// the chain after the top-5000 pre-filter: the user's sampler order and XTC over the candidates in c
+inline Cands apply_order(Cands c, int n_ctx, const Params &P, const std::vector<int> &last_n, std::mt19937 &rng,
                          bool stop_before_order) {
-    cand.clear();
-    cand.reserve(n_vocab);
-    for (int t = 0; t < n_vocab; ++t) cand.push_back(TokData{t, logits[t], 0.0f});
-    for (const LogitBias &b : biases) cand[b.token_id].logit += b.bias;
-    Cands c{cand.data(), cand.size(), false};
-    dry(n_ctx, P.dry_penalty_last_n, P.dry_multiplier, P.dry_base, P.dry_allowed_length, restarts, ctx_tokens, &c);
-    top_k(&c, 5000);
     if (stop_before_order) return c;
     for (int s : P.order) {
         switch (s) {
@@ -456,6 +451,34 @@ inline Cands apply_chain(std::vector<TokData> &cand, const float *logits, int n_
     return c;
 }
 
+// the candidate chain of SampleLogits up to (not including) the final draw: biases, DRY, top-5000, then the
+// user's sampler order and XTC.  `cand` holds the candidates; returns the array view.  (mirostat: not here)
+inline Cands apply_chain(std::vector<TokData> &cand, const float *logits, int n_ctx, int n_vocab, const Params &P,
+                         const std::vector<LogitBias> &biases, const RestartSeqs &restarts,
+                         const std::vector<int> &ctx_tokens, const std::vector<int> &last_n, std::mt19937 &rng,
+                         bool stop_before_order) {
+    cand.clear();
+    cand.reserve(n_vocab);
+    for (int t = 0; t < n_vocab; ++t) cand.push_back(TokData{t, logits[t], 0.0f});
+    for (const LogitBias &b : biases) cand[b.token_id].logit += b.bias;
+    Cands c{cand.data(), cand.size(), false};
+    dry(n_ctx, P.dry_penalty_last_n, P.dry_multiplier, P.dry_base, P.dry_allowed_length, restarts, ctx_tokens, &c);
+    top_k(&c, 5000);
+    return apply_order(c, n_ctx, P, last_n, rng, stop_before_order);
+}
+
+// the end of SampleLogits over the chain's candidates: mirostat's own steps, or the draw
+inline int sample_tail(Cands c, int n_ctx, int n_vocab, const Params &P, const std::vector<int> &last_n, std::mt19937 &rng,
+                       float *mirostat_mu) {
+    if (P.mirostat == 1 || P.mirostat == 2) {
+        rep_pen(n_ctx, P.rep_pen_range, P.rep_pen, P.rep_pen_slope, P.presence_penalty, last_n, &c);
+        temperature(&c, P.temp, P.smoothing_factor);
+        if (P.mirostat == 1) return mirostat_v1(n_vocab, &c, rng, P.mirostat_tau, P.mirostat_eta, 100, mirostat_mu);
+        return mirostat_v2(&c, rng, P.mirostat_tau, P.mirostat_eta, mirostat_mu);
+    }
+    return draw(&c, rng);
+}
+
 // SampleLogits, gpttype_adapter.cpp:1338-1434 (grammar omitted).  `logits` already carries the EOS /
 // banned-token suppression the caller applies (gpttype_adapter.cpp:3200-3224).  mirostat_mu is the
 // function-static of the reference (initialised once per process to 2 * tau).
@@ -465,13 +488,16 @@ inline int sample_logits(const float *logits, int n_ctx, int n_vocab, const Para
     std::vector<TokData> cand;
     const bool miro = P.mirostat == 1 || P.mirostat == 2;
     Cands c = apply_chain(cand, logits, n_ctx, n_vocab, P, biases, restarts, ctx_tokens, last_n, rng, miro);
-    if (miro) {
-        rep_pen(n_ctx, P.rep_pen_range, P.rep_pen, P.rep_pen_slope, P.presence_penalty, last_n, &c);
-        temperature(&c, P.temp, P.smoothing_factor);
-        if (P.mirostat == 1) return mirostat_v1(n_vocab, &c, rng, P.mirostat_tau, P.mirostat_eta, 100, mirostat_mu);
-        return mirostat_v2(&c, rng, P.mirostat_tau, P.mirostat_eta, mirostat_mu);
-    }
-    return draw(&c, rng);
+    return sample_tail(c, n_ctx, n_vocab, P, last_n, rng, mirostat_mu);
+}
+
+// SampleLogits from the top-5000 candidates a device front end and kcand::top_k_from_survivors left in cand (cand.h):
+// biases, DRY and the pre-filter are already in them; the rest of the chain is the one above.
+inline int sample_candidates(std::vector<TokData> &cand, int n_ctx, int n_vocab, const Params &P, const std::vector<int> &last_n,
+                             std::mt19937 &rng, float *mirostat_mu) {
+    const bool miro = P.mirostat == 1 || P.mirostat == 2;
+    Cands c = apply_order(Cands{cand.data(), cand.size(), true}, n_ctx, P, last_n, rng, miro);
+    return sample_tail(c, n_ctx, n_vocab, P, last_n, rng, mirostat_mu);
 }
 
 // LowestLogit, gpttype_adapter.cpp:294-303

@@ -156,10 +156,19 @@ _SIGS = {
     "kcpp_rope_qk_inplace": [P, I64, I, I, I, I, I, P, P, P],
     "kcpp_kv_store_q": [I, I, P, I64, I64, I64, I, I64, P, P, I64, I, P, P],
     "kcpp_flash_attn_q": [I, I, P, I64, P, P, P, I, I, I, I, I64, I, P, Fl, P],
+    "kcpp_logit_candidates": [P, I, I, P, I, P, I, P, I, P, P, P, I, P],
+    "kcpp_model_candidates": [P, I, P, I, P, I, P, I, P, P, P, I],
+    "kcpp_cand_plan": [I64, P],
+    "kcpp_cand_front_ref": [P, I, I, P, I, P, I, P, I, P, P, P, I],
+    "kcpp_expose_set_sample_front": [I],
+    "kcpp_expose_sample_front_stats": [P],
+    "kcpp_expose_last_tokens": [P, I],
+    "kcpp_expose_mirostat_mu": [I, Fl],
 }
 _RES = {"kcpp_gradient_ai_rope_base": Fl, "kcpp_q6p_image_bytes": I64, "kcpp_model_fused_route_count": I64, "kcpp_model_moe_grouped_count": I64, "kcpp_gemm_grouped_ws_bytes": I64, "kcpp_fa_split_ws_bytes": I64, "kcpp_q80t_ws_bytes": I64, "kcpp_act_bytes": I64, "kcpp_fa_ext_workspace_bytes": I64, "kcpp_fa_workspace_bytes": I64, "kcpp_gemm_workspace_bytes": I64,
         "kcpp_model_create": P, "kcpp_model_hidden": P, "kcpp_model_stream": P, "kcpp_model_weight_bytes": I64,
-        "kcpp_last_error": ctypes.c_char_p, "kcpp_model_free": None, "kcpp_fa_set_stamps": None}
+        "kcpp_last_error": ctypes.c_char_p, "kcpp_model_free": None, "kcpp_fa_set_stamps": None,
+        "kcpp_expose_set_sample_front": None, "kcpp_expose_sample_front_stats": None, "kcpp_expose_mirostat_mu": Fl}
 _L.kcpp_act_bytes.argtypes = [I, I64, I64]
 _L.kcpp_kv_cache_bytes.argtypes = [I, I64, I64]
 _L.kcpp_kv_cache_bytes.restype = I64
@@ -572,6 +581,47 @@ def gemv_qkv_dual_plan(qtype, K, Na, Nb, flags_a=(), flags_b=(), Kb=None):
                                     nb, _gemv_flags(flags_b), out)
     return rc if rc else dict(zip(("rc", "nblk", "lds_bytes", "a_nblk", "a_lds_bytes", "a_NI", "b_nblk", "b_lds_bytes", "b_IT"),
                                   out))
+
+
+class CandHdr(ctypes.Structure):
+    """struct kcpp_cand_hdr: the sampling front end's result header"""
+    _fields_ = [("low", Fl), ("ib", ctypes.c_int32), ("nhave", ctypes.c_int32), ("n_bad", ctypes.c_int32),
+                ("hist", ctypes.c_int32 * 128)]
+
+
+CAND_GUARD_ID, CAND_GUARD_BITS = -77, 0x7FC0DEAD       # what candidates() leaves in entries the call did not write
+
+
+def cand_plan(n):
+    """the sampling front end's launch plan for n logits (kcpp_cand_plan; host only): dict of slice, block, nblk"""
+    out = (ctypes.c_int32 * 4)()
+    _chk(_L.kcpp_cand_plan(int(n), out), "cand_plan")
+    return dict(zip(("rc", "slice", "block", "nblk"), out))
+
+
+def candidates(where, logits, k, set_ids=(), adds=(), subs=(), cap=16384, guard=0, stream=None):
+    """The sampling front end on n logits: set_ids set to the lowest logit, adds / subs = [(id, value), ...] added /
+    subtracted in list order, then the candidates at or above top_k(k)'s bucket cut.  where: "ref" (the CPU model,
+    logits a float32 array), "dev" (kcpp_logit_candidates, logits = (device address, n)) or a Model (its last logits).
+    Returns (CandHdr, ids, vals): int32 / float32 arrays of cap + guard entries, min(nhave, cap) of them written and the
+    rest left at CAND_GUARD_ID / CAND_GUARD_BITS"""
+    import numpy as np
+    edit = np.dtype([("id", np.int32), ("v", np.float32)])
+    s = np.ascontiguousarray(set_ids, dtype=np.int32)
+    a, b = np.array(list(adds), dtype=edit), np.array(list(subs), dtype=edit)
+    hdr = CandHdr()
+    ids = np.full(cap + guard, CAND_GUARD_ID, np.int32)
+    vals = np.full(cap + guard, CAND_GUARD_BITS, np.uint32).view(np.float32)
+    lists = (s.ctypes.data_as(P), len(s), a.ctypes.data_as(P), len(a), b.ctypes.data_as(P), len(b), ctypes.byref(hdr),
+             ids.ctypes.data_as(P), vals.ctypes.data_as(P), int(cap))
+    if isinstance(where, Model):
+        _chk(_L.kcpp_model_candidates(where.m, int(k), *lists), "model_candidates")
+    elif where == "dev":
+        _chk(_L.kcpp_logit_candidates(logits[0], int(logits[1]), int(k), *lists, stream), "logit_candidates")
+    else:
+        lg = np.ascontiguousarray(logits, dtype=np.float32)
+        _chk(_L.kcpp_cand_front_ref(lg.ctypes.data_as(P), len(lg), int(k), *lists), "cand_front_ref")
+    return hdr, ids, vals
 
 
 def pipeline_trace(n_stages, ubatch, T, n_past, steps):
