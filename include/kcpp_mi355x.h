@@ -470,6 +470,34 @@ int kcpp_cand_plan(int64_t n, int32_t out[4]);
 int kcpp_cand_front_ref(const float *logits, int n, int k, const int32_t *set_ids, int n_set, const kcpp_cand_edit *adds,
                         int n_add, const kcpp_cand_edit *subs, int n_sub, kcpp_cand_hdr *hdr_out, int32_t *ids_out,
                         float *logits_out, int cap);
+/* The same with a grammar's reject mask ((n + 31) / 32 host words, bit i % 32 of word i / 32 set: id i is rejected).  A
+ * rejected id counts as -inf, what the reference's sample_grammar writes between the biases and DRY: bucket 0, never
+ * returned, counted in n_rej and not in n_bad (its edited value counts in n_bad as it would without a mask).  When the
+ * cut is bucket 0 (ib == 0: fewer than k candidates above it) nhave is n - n_rej and every id that is not rejected
+ * comes back: the host rebuilds the n-entry array (rejected = -inf) for the full chain.  The entries without a mask
+ * and their results are unchanged. */
+typedef struct kcpp_cand_hdr_masked {
+    kcpp_cand_hdr h;
+    int32_t n_rej;          /* ids the mask rejects */
+    int32_t pad;
+} kcpp_cand_hdr_masked;
+int kcpp_logit_candidates_masked(const float *logits_dev, int n, int k, const int32_t *set_ids, int n_set,
+                                 const kcpp_cand_edit *adds, int n_add, const kcpp_cand_edit *subs, int n_sub,
+                                 const uint32_t *mask, kcpp_cand_hdr_masked *hdr_out, int32_t *ids_out, float *logits_out,
+                                 int cap, void *stream);
+int kcpp_model_candidates_masked(kcpp_model *m, int k, const int32_t *set_ids, int n_set, const kcpp_cand_edit *adds,
+                                 int n_add, const kcpp_cand_edit *subs, int n_sub, const uint32_t *mask,
+                                 kcpp_cand_hdr_masked *hdr_out, int32_t *ids_out, float *logits_out, int cap);
+int kcpp_cand_front_ref_masked(const float *logits, int n, int k, const int32_t *set_ids, int n_set,
+                               const kcpp_cand_edit *adds, int n_add, const kcpp_cand_edit *subs, int n_sub,
+                               const uint32_t *mask, kcpp_cand_hdr_masked *hdr_out, int32_t *ids_out, float *logits_out,
+                               int cap);
+/* greedy token under a reject mask: argmax over the ids the mask allows, the lowest id among equal logits (the rule of
+ * kcpp_model_argmax).  *token_out = -1 when every id is rejected; *logit_out (may be null) the token's logit.  Leaves
+ * the stage's own argmax slot and token input alone.  kcpp_logit_argmax_masked: the same on any device buffer. */
+int kcpp_model_argmax_masked(kcpp_model *m, const uint32_t *mask_host, int32_t *token_out, float *logit_out);
+int kcpp_logit_argmax_masked(const float *logits_dev, int n, const uint32_t *mask_host, int32_t *token_out, float *logit_out,
+                             void *stream);
 /* wait for all work queued on the stage's stream */
 int kcpp_model_sync(kcpp_model *m);
 /* per-stage step without embedding/out: run layers on the hidden buffer for T tokens */
@@ -603,6 +631,14 @@ int kcpp_sampler_probe_front(const float *logits, int n_vocab, int n_ctx, const 
                              const int *restarts, int n_restart_ints, unsigned seed, float *mu, int *out_ids, float *out_p,
                              int cap, int *out_n, const int *set_ids, int n_set, const int *add_ids, const float *add_v,
                              int n_add, const int *sub_ids, const float *sub_v, int n_sub, int *status_out);
+/* the same under a grammar's reject mask ((n_vocab + 31) / 32 words): the masked CPU model, then the bucket tail
+ * (*status_out 0) or, with the cut in bucket 0, the rebuilt n_vocab-entry array through the chain's own top_k (4) */
+int kcpp_sampler_probe_front_masked(const float *logits, int n_vocab, int n_ctx, const float *fp, const int *ip,
+                                    const int *order, int n_order, const int *ctx_toks, int n_ctx_toks, const int *last_n,
+                                    int n_last, const int *restarts, int n_restart_ints, unsigned seed, float *mu, int *out_ids,
+                                    float *out_p, int cap, int *out_n, const int *set_ids, int n_set, const int *add_ids,
+                                    const float *add_v, int n_add, const int *sub_ids, const float *sub_v, int n_sub,
+                                    const uint32_t *mask, int *status_out);
 /* generate()'s sampled tokens start from the device's candidates (kcpp_model_candidates) instead of a read of every
  * logit: on 1 / off 0 for the calls that follow, -1 = the environment's answer (KCPP_SAMPLE_DEV, read per call; unset:
  * on).  The drawn tokens are the same either way. */
@@ -610,6 +646,29 @@ void kcpp_expose_set_sample_front(int on);
 /* out = {tokens sampled through the front end, fallbacks to the full read for n_bad, for nhave > capacity, for a host /
  * device bucket mismatch} since the last call; reading resets them */
 void kcpp_expose_sample_front_stats(int64_t out[4]);
+/* Grammar-constrained requests (generate()'s grammar / grammar_retain_state; koboldcpp_amd/csrc/grammar.h).
+ * out = {sampling steps with a grammar, greedy tokens the grammar took as the device argmax stands (no mask built),
+ * masked argmax runs (the device argmax was rejected), sampled tokens rebuilt from every allowed candidate (the front
+ * end's cut in bucket 0), fallbacks to the full read under a grammar, sampled tokens through the front end's bucket
+ * tail under a grammar} since the last call; reading resets them */
+void kcpp_expose_grammar_stats(int64_t out[6]);
+/* host milliseconds spent building reject masks during the last generate() */
+double kcpp_expose_grammar_mask_ms(void);
+/* test hooks, host only: a grammar outside generate().  create: null when the text gives no grammar (syntax error,
+ * undefined rule, left recursion, a size limit).  rules: the (type, value) element pairs rule after rule (types 0 END,
+ * 1 ALT, 2 RULE_REF, 3 CHAR, 4 CHAR_NOT, 5 CHAR_RNG_UPPER, 6 CHAR_ALT, 7 CHAR_ANY), returns the rule count.  reject:
+ * the reject bitmask over n pieces (piece i = blob[off[i] .. off[i + 1])), returns the rejected count; use_cache picks
+ * the decoded-once vocabulary over the per-step decode (same mask).  accept_piece: 0, -1 (EOS while the grammar is
+ * incomplete), -2 (no stack took the piece).  partial: {value, n_remain} of the carried UTF-8 character. */
+typedef struct kcpp_grammar kcpp_grammar;
+kcpp_grammar *kcpp_grammar_create(const char *text);
+void kcpp_grammar_free(kcpp_grammar *g);
+int kcpp_grammar_rules(const kcpp_grammar *g, uint32_t *elems, int cap_elems, int32_t *rule_len, int cap_rules, int *n_elems);
+int kcpp_grammar_n_stacks(const kcpp_grammar *g);
+int kcpp_grammar_reject(kcpp_grammar *g, const uint8_t *blob, const int64_t *off, int n, int eos, int eot, int use_cache,
+                        uint32_t *mask_out);
+int kcpp_grammar_accept_piece(kcpp_grammar *g, const uint8_t *piece, int len, int is_eos);
+void kcpp_grammar_partial(const kcpp_grammar *g, int64_t out[2]);
 /* test hook: SampleLogits' process-lifetime mirostat_mu (the reference's function-static); set != 0 assigns value
  * first; returns the current mu.  Lets one process run the same mirostat request twice from the same state */
 float kcpp_expose_mirostat_mu(int set, float value);

@@ -53,6 +53,11 @@ struct Hdr {                             // the result header
     int32_t n_bad;                       // > 0: the host's bucket of some value is not defined; fall back
     int32_t hist[CAND_NB];
 };
+struct HdrM {                            // the masked entries' header: the old one, then the mask's counts
+    Hdr h;                               // with ib == 0: nhave = n - n_rej (every non-rejected id comes back)
+    int32_t n_rej;                       // ids the mask rejects
+    int32_t pad;
+};
 struct Pair { int32_t id; float v; };    // a survivor as the device writes it
 // an edit as the device walks it: sorted by (id, kind), list order kept within a kind
 enum { CAND_SET = 0, CAND_ADD = 1, CAND_SUB = 2 };
@@ -72,7 +77,8 @@ inline int plan(int64_t n, Plan *p) {
 
 // device workspace of one front end for up to n logits, max_ops edits and cap survivors: byte offsets into one
 // allocation (every part 16-byte aligned)
-struct WsLayout { size_t scratch, minpart, hist, bad, off, low, ops, out, bytes; };
+struct WsLayout { size_t scratch, minpart, hist, bad, off, low, ops, out, mask, rej, bytes; };
+inline size_t mask_words(int64_t n) { return (size_t)((n + 31) / 32); }
 inline WsLayout ws_layout(int64_t n, int64_t max_ops, int64_t cap) {
     Plan p;
     plan(std::max<int64_t>(1, std::min<int64_t>(n, CAND_MAX_N)), &p);
@@ -86,7 +92,9 @@ inline WsLayout ws_layout(int64_t n, int64_t max_ops, int64_t cap) {
     w.off = take((size_t)p.nblk * 4);
     w.low = take(4);
     w.ops = take((size_t)max_ops * sizeof(Op));
-    w.out = take(sizeof(Hdr) + (size_t)cap * sizeof(Pair));
+    w.out = take(sizeof(HdrM) + (size_t)cap * sizeof(Pair));
+    w.mask = take(mask_words(n) * 4);
+    w.rej = take((size_t)p.nblk * 4);
     w.bytes = at;
     return w;
 }
@@ -99,7 +107,9 @@ struct Args {
     int nops, n_set;
     float *scratch, *minpart, *low;
     int32_t *hist, *bad, *off;
-    void *out;                           // Hdr, then cap Pairs
+    void *out;                           // Hdr, then cap Pairs; with a mask: HdrM, then cap Pairs
+    const uint32_t *mask;                // null, or (n + 31) / 32 words: bit i % 32 of word i / 32 set = id i rejected
+    int32_t *rej;                        // with a mask: per-slice rejected counts
 };
 
 // the edit lists as one sorted program: ops by (id, kind) with the list order kept within a kind, repeated set-low ids
@@ -145,8 +155,10 @@ inline bool value_bad(float v) { return !std::isfinite(v) || !(std::fabs(bucket_
 
 // the device pass on the CPU: header and the first min(nhave, cap) survivors (id, logit) in ascending id.
 // Returns 0, or -1 / -2 as build_ops and plan do.
-inline int cand_front_ref(const float *logits, int n, int k, const int32_t *set_ids, int n_set, const Edit *adds, int n_add,
-                          const Edit *subs, int n_sub, Hdr *hdr, std::vector<int32_t> &ids, std::vector<float> &vals, int cap) {
+// mask: null, or the reject bitmask; *n_rej its count over [0, n).
+inline int cand_front_ref_masked(const float *logits, int n, int k, const int32_t *set_ids, int n_set, const Edit *adds,
+                                 int n_add, const Edit *subs, int n_sub, const uint32_t *mask, Hdr *hdr, int32_t *n_rej,
+                                 std::vector<int32_t> &ids, std::vector<float> &vals, int cap) {
     Plan p;
     if (plan(n, &p)) return -2;
     std::vector<uint64_t> keys;
@@ -169,8 +181,11 @@ inline int cand_front_ref(const float *logits, int n, int k, const int32_t *set_
     *hdr = Hdr{};
     hdr->low = low;
     std::vector<uint8_t> b(n);
+    int nrej = 0;
+    auto rejected = [&](int i) { return mask && ((mask[i >> 5] >> (i & 31)) & 1u); };
     for (int i = 0; i < n; ++i) {
-        b[i] = (uint8_t)bucket_of(bucket_f(e[i]));
+        b[i] = rejected(i) ? 0 : (uint8_t)bucket_of(bucket_f(e[i]));
+        nrej += rejected(i);
         ++hdr->hist[b[i]];
         if (value_bad(e[i]) || (n_set > 0 && !std::isfinite(logits[i]))) ++hdr->n_bad;
     }
@@ -180,11 +195,33 @@ inline int cand_front_ref(const float *logits, int n, int k, const int32_t *set_
         nhave += hdr->hist[ib];
         if (nhave >= k) break;
     }
+    if (mask && ib == 0) nhave = n - nrej;
     hdr->ib = ib, hdr->nhave = nhave;
+    if (n_rej) *n_rej = nrej;
     ids.clear(), vals.clear();
     for (int i = 0; i < n && (int)ids.size() < cap; ++i)
-        if (b[i] >= ib) { ids.push_back(i); vals.push_back(e[i]); }
+        if (b[i] >= ib && !rejected(i)) { ids.push_back(i); vals.push_back(e[i]); }
     return 0;
+}
+inline int cand_front_ref(const float *logits, int n, int k, const int32_t *set_ids, int n_set, const Edit *adds, int n_add,
+                          const Edit *subs, int n_sub, Hdr *hdr, std::vector<int32_t> &ids, std::vector<float> &vals, int cap) {
+    return cand_front_ref_masked(logits, n, k, set_ids, n_set, adds, n_add, subs, n_sub, nullptr, hdr, nullptr, ids, vals, cap);
+}
+
+// The cut in bucket 0 under a mask: the n-entry candidate array the full chain would have had after sample_grammar --
+// rejected ids -inf, every other id its edited value from the front end -- ready for ksamp::top_k(k).  false: the
+// survivors are not exactly the non-rejected ids in ascending order (the caller runs the full chain).
+inline bool rebuild_masked(const Hdr &hdr, int n_rej, const uint32_t *mask, const int32_t *ids, const float *vals, int nsurv,
+                           int n, std::vector<ksamp::TokData> &out) {
+    if (hdr.ib != 0 || nsurv != hdr.nhave || nsurv != n - n_rej) return false;
+    out.resize(n);
+    int at = 0;
+    for (int i = 0; i < n; ++i) {
+        if ((mask[i >> 5] >> (i & 31)) & 1u) { out[i] = ksamp::TokData{i, -INFINITY, 0.0f}; continue; }
+        if (at >= nsurv || ids[at] != i) return false;
+        out[i] = ksamp::TokData{i, vals[at++], 0.0f};
+    }
+    return at == nsurv;
 }
 
 // The tail of ksamp::top_k(c, k) for k > 128 from a front-end result: scatter into per-bucket runs, the sorts, take k.

@@ -76,20 +76,33 @@ __global__ void __launch_bounds__(CAND_BLOCK) k_cand_apply(const Op *__restrict_
     scratch[id] = v;
 }
 
-// hist[slice][128], bad[slice]; raw: the unedited logits when their finiteness counts too (a set-low list), else null
+// is id rejected: bit id % 32 of word id / 32 (32 consecutive ids share a word, a wave reads two)
+__device__ __forceinline__ bool cand_rejected(const uint32_t *__restrict__ mask, int id) {
+    return (mask[id >> 5] >> (id & 31)) & 1u;
+}
+
+// hist[slice][128], bad[slice]; raw: the unedited logits when their finiteness counts too (a set-low list), else null.
+// MASKED: a rejected id goes to bucket 0 whatever its value and is counted in rej[slice]; bad counts as without a mask
+template <bool MASKED>
 __global__ void __launch_bounds__(CAND_BLOCK) k_cand_hist(const float *__restrict__ e, const float *__restrict__ raw, int n,
-                                                          int32_t *__restrict__ hist, int32_t *__restrict__ bad) {
+                                                          int32_t *__restrict__ hist, int32_t *__restrict__ bad,
+                                                          const uint32_t *__restrict__ mask, int32_t *__restrict__ rej) {
     __shared__ int h[CAND_NB];
-    __shared__ int nbad;
+    __shared__ int nbad, nrej;
     if (threadIdx.x < CAND_NB) h[threadIdx.x] = 0;
-    if (threadIdx.x == 0) nbad = 0;
+    if (threadIdx.x == 0) nbad = 0, nrej = 0;
     __syncthreads();
     const int base = blockIdx.x * CAND_SLICE;
     for (int it = 0; it < ITERS; ++it) {
         const int id = base + it * CAND_BLOCK + threadIdx.x;
         if (id < n) {
             const float v = e[id], f = cand_f(v);
-            atomicAdd(&h[cand_bucket(f)], 1);
+            if (MASKED && cand_rejected(mask, id)) {
+                atomicAdd(&h[0], 1);
+                atomicAdd(&nrej, 1);
+            } else {
+                atomicAdd(&h[cand_bucket(f)], 1);
+            }
             bool b = !cand_finite(v) || !(fabsf(f) < 2147483648.0f);
             if (raw) b = b || !cand_finite(raw[id]);
             if (b) atomicAdd(&nbad, 1);
@@ -97,19 +110,23 @@ __global__ void __launch_bounds__(CAND_BLOCK) k_cand_hist(const float *__restric
     }
     __syncthreads();
     if (threadIdx.x < CAND_NB) hist[(size_t)blockIdx.x * CAND_NB + threadIdx.x] = h[threadIdx.x];
-    if (threadIdx.x == 0) bad[blockIdx.x] = nbad;
+    if (threadIdx.x == 0) {
+        bad[blockIdx.x] = nbad;
+        if (MASKED) rej[blockIdx.x] = nrej;
+    }
 }
 
 // one workgroup: totals, the walk from bucket 127 down to the cut, the header, and each slice's survivor count scanned
-// into its offset
+// into its offset.  MASKED: hdr is an HdrM; with the cut in bucket 0 the survivors are the ids that are not rejected
+template <bool MASKED>
 __global__ void __launch_bounds__(CAND_BLOCK) k_cand_cut(const int32_t *__restrict__ hist, const int32_t *__restrict__ bad,
                                                          int nblk, int k, const float *__restrict__ low, Hdr *__restrict__ hdr,
-                                                         int32_t *__restrict__ off) {
+                                                         int32_t *__restrict__ off, const int32_t *__restrict__ rej) {
     __shared__ int tot[CAND_NB];
     __shared__ int sc[CAND_BLOCK];
-    __shared__ int s_ib, s_bad;
+    __shared__ int s_ib, s_bad, s_rej;
     const int t = threadIdx.x;
-    if (t == 0) s_bad = 0;
+    if (t == 0) s_bad = 0, s_rej = 0;
     __syncthreads();
     if (t < CAND_NB) {
         int s = 0;
@@ -119,6 +136,11 @@ __global__ void __launch_bounds__(CAND_BLOCK) k_cand_cut(const int32_t *__restri
         int s = 0;
         for (int b = t - CAND_NB; b < nblk; b += CAND_BLOCK - CAND_NB) s += bad[b];
         if (s) atomicAdd(&s_bad, s);
+        if (MASKED) {
+            int r = 0;
+            for (int b = t - CAND_NB; b < nblk; b += CAND_BLOCK - CAND_NB) r += rej[b];
+            if (r) atomicAdd(&s_rej, r);
+        }
     }
     __syncthreads();
     if (t == 0) {
@@ -128,6 +150,12 @@ __global__ void __launch_bounds__(CAND_BLOCK) k_cand_cut(const int32_t *__restri
             if (nhave >= k) break;
         }
         if (ib == 0) nhave += tot[0];          // k <= n: the walk ends at bucket 0 at the latest
+        if (MASKED) {
+            if (ib == 0) nhave -= s_rej;
+            HdrM *hm = (HdrM *)hdr;
+            hm->n_rej = s_rej;
+            hm->pad = 0;
+        }
         s_ib = ib;
         hdr->low = low ? *low : 0.0f;
         hdr->ib = ib;
@@ -144,6 +172,7 @@ __global__ void __launch_bounds__(CAND_BLOCK) k_cand_cut(const int32_t *__restri
     for (int b = b0; b < b1; ++b) {
         int c = 0;
         for (int j = ib; j < CAND_NB; ++j) c += hist[(size_t)b * CAND_NB + j];
+        if (MASKED && ib == 0) c -= rej[b];
         off[b] = c;
         mine += c;
     }
@@ -163,9 +192,12 @@ __global__ void __launch_bounds__(CAND_BLOCK) k_cand_cut(const int32_t *__restri
     }
 }
 
-// the slice's survivors (bucket >= ib) to pairs[off[slice] ...] in ascending id, nothing at or past cap
+// the slice's survivors (bucket >= ib; MASKED: and not rejected) to pairs[off[slice] ...] in ascending id, nothing at
+// or past cap
+template <bool MASKED>
 __global__ void __launch_bounds__(CAND_BLOCK) k_cand_compact(const float *__restrict__ e, int n, const Hdr *__restrict__ hdr,
-                                                             const int32_t *__restrict__ off, Pair *__restrict__ pairs, int cap) {
+                                                             const int32_t *__restrict__ off, Pair *__restrict__ pairs, int cap,
+                                                             const uint32_t *__restrict__ mask) {
     __shared__ int wc[WAVES];
     const int ib = hdr->ib;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -178,16 +210,17 @@ __global__ void __launch_bounds__(CAND_BLOCK) k_cand_compact(const float *__rest
         if (id < n) {
             v = e[id];
             keep = cand_bucket(cand_f(v)) >= ib;
+            if (MASKED) keep = keep && !cand_rejected(mask, id);
         }
-        const unsigned long long mask = __ballot(keep);
-        if (lane == 0) wc[wave] = __popcll(mask);
+        const unsigned long long kept = __ballot(keep);
+        if (lane == 0) wc[wave] = __popcll(kept);
         __syncthreads();
         int before = 0, total = 0;
         for (int w = 0; w < WAVES; ++w) {
             if (w < wave) before += wc[w];
             total += wc[w];
         }
-        const int pos = run + before + __popcll(mask & ((1ull << lane) - 1ull));
+        const int pos = run + before + __popcll(kept & ((1ull << lane) - 1ull));
         if (keep && pos >= 0 && pos < cap) pairs[pos] = Pair{id, v};
         run += total;
         __syncthreads();
@@ -199,7 +232,8 @@ __global__ void __launch_bounds__(CAND_BLOCK) k_cand_compact(const float *__rest
 int kcpp_cand_launch(const Plan &p, const Args &a, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     if (p.rc || p.nblk < 1 || a.n < 1 || (int64_t)p.nblk * CAND_SLICE < a.n || a.k < 1 || a.k > a.n || a.cap < 0 || a.nops < 0 ||
-        !a.logits || !a.hist || !a.bad || !a.off || !a.out || (a.nops > 0 && (!a.ops || !a.scratch || !a.minpart || !a.low)))
+        !a.logits || !a.hist || !a.bad || !a.off || !a.out || (a.nops > 0 && (!a.ops || !a.scratch || !a.minpart || !a.low)) ||
+        (a.mask && !a.rej))
         return -2;
     const float *e = a.logits;
     if (a.nops > 0) {
@@ -209,10 +243,20 @@ int kcpp_cand_launch(const Plan &p, const Args &a, void *stream) {
         e = a.scratch;
     }
     Hdr *hdr = (Hdr *)a.out;
-    hipLaunchKernelGGL(k_cand_hist, dim3(p.nblk), dim3(CAND_BLOCK), 0, s, e, a.n_set > 0 ? a.logits : (const float *)nullptr, a.n,
-                       a.hist, a.bad);
-    hipLaunchKernelGGL(k_cand_cut, dim3(1), dim3(CAND_BLOCK), 0, s, a.hist, a.bad, p.nblk, a.k,
-                       a.nops > 0 ? a.low : (const float *)nullptr, hdr, a.off);
-    hipLaunchKernelGGL(k_cand_compact, dim3(p.nblk), dim3(CAND_BLOCK), 0, s, e, a.n, hdr, a.off, (Pair *)(hdr + 1), a.cap);
+    const float *raw = a.n_set > 0 ? a.logits : (const float *)nullptr;
+    const float *low = a.nops > 0 ? a.low : (const float *)nullptr;
+    if (a.mask) {
+        Pair *pairs = (Pair *)((HdrM *)a.out + 1);
+        hipLaunchKernelGGL(k_cand_hist<true>, dim3(p.nblk), dim3(CAND_BLOCK), 0, s, e, raw, a.n, a.hist, a.bad, a.mask, a.rej);
+        hipLaunchKernelGGL(k_cand_cut<true>, dim3(1), dim3(CAND_BLOCK), 0, s, a.hist, a.bad, p.nblk, a.k, low, hdr, a.off, a.rej);
+        hipLaunchKernelGGL(k_cand_compact<true>, dim3(p.nblk), dim3(CAND_BLOCK), 0, s, e, a.n, hdr, a.off, pairs, a.cap, a.mask);
+    } else {
+        hipLaunchKernelGGL(k_cand_hist<false>, dim3(p.nblk), dim3(CAND_BLOCK), 0, s, e, raw, a.n, a.hist, a.bad,
+                           (const uint32_t *)nullptr, (int32_t *)nullptr);
+        hipLaunchKernelGGL(k_cand_cut<false>, dim3(1), dim3(CAND_BLOCK), 0, s, a.hist, a.bad, p.nblk, a.k, low, hdr, a.off,
+                           (const int32_t *)nullptr);
+        hipLaunchKernelGGL(k_cand_compact<false>, dim3(p.nblk), dim3(CAND_BLOCK), 0, s, e, a.n, hdr, a.off, (Pair *)(hdr + 1),
+                           a.cap, (const uint32_t *)nullptr);
+    }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -39,6 +39,7 @@
 #include "../../include/kcpp_synth.h"
 #include "cand.h"
 #include "gguf.h"
+#include "grammar.h"
 #include "kcpp_internal.h"
 #include "sampler.h"
 #include "tokenizer.h"
@@ -104,6 +105,15 @@ struct Engine {
     std::vector<kcpp_cand_edit> f_add, f_sub;
     std::vector<float> f_vals;
     std::vector<ksamp::TokData> f_cand;
+    // grammar (grammar.h): the vocabulary's pieces and their code points, decoded on the first constrained request; the
+    // reject mask of the current step (g_nrej < 0: not built yet)
+    std::vector<std::string> g_pieces;
+    std::vector<const char *> g_ptr;
+    std::vector<size_t> g_len;
+    kgram::VocabCache g_vocab;
+    kgram::MaskWork g_work;
+    std::vector<uint32_t> g_mask;
+    int g_nrej = -1;
     ~Engine() {
         for (size_t s = 0; s < stages.size(); ++s) {
             hipSetDevice(devs[s]);
@@ -133,6 +143,13 @@ constexpr bool kSampleFrontDefault = true;
 int g_front_override = -1;
 int64_t g_front_stats[4] = {0, 0, 0, 0};    // tokens through the front end; fallbacks: n_bad, overflow, mismatch
 std::vector<int> g_last_tokens;             // the token ids of the last generate() (kcpp_expose_last_tokens)
+// the grammar of the current request and its state (the reference's globals grammar / current_grammar: they outlive a
+// request, which is what grammar_retain_state continues)
+kgram::Grammar g_gram;
+// steps with a grammar; greedy tokens the grammar took without a mask; masked argmax runs; sampled tokens rebuilt from
+// every allowed candidate (cut in bucket 0); full-read fallbacks under a grammar; sampled tokens through the bucket tail
+int64_t g_gram_stats[6] = {0, 0, 0, 0, 0, 0};
+double g_gram_mask_ms = 0;                  // host time in reject_mask() since the last generate() began
 
 const char *tname(int il, int j) {
     static const char *n[9] = {"attn_norm", "attn_q", "attn_k", "attn_v", "attn_output", "ffn_norm", "ffn_gate", "ffn_up", "ffn_down"};
@@ -595,8 +612,11 @@ bool chain_is_argmax(const SamplerSetup &S) {
 // have; the rest of the chain is unchanged.  1: *tok is the token; 0: fall back to the full read (a value whose bucket
 // the host does not define, more survivors than the capacity, or the host's buckets disagreeing with the device's;
 // nothing has been drawn from rng); < 0: a device error.
+// mask: null, or the grammar's reject mask of this step (kcpp_model_candidates_masked): with the cut above bucket 0 the
+// survivors are what top_k(5000) keeps of the masked array and the tail is the same; with the cut in bucket 0 every
+// allowed candidate came back and the n_vocab-entry array is rebuilt for ksamp::top_k (kcand::rebuild_masked).
 int sample_front(Engine &e, const SamplerSetup &S, const std::vector<int> &last_n, std::mt19937 &rng, float *mu,
-                 const std::vector<int> *slop, int *tok) {
+                 const std::vector<int> *slop, const uint32_t *mask, int *tok) {
     const int nv = e.hp.n_vocab, eos = e.tok.eos(), eot = e.tok.eot();
     e.f_set.clear(), e.f_add.clear(), e.f_sub.clear();
     if (S.suppress_eos && eos >= 0 && eos < nv) e.f_set.push_back(eos);
@@ -612,21 +632,72 @@ int sample_front(Engine &e, const SamplerSetup &S, const std::vector<int> &last_
         e.f_sub.push_back(kcpp_cand_edit{d.id, d.penalty});
     e.f_ids.resize(kcand::CAND_CAP), e.f_vals.resize(kcand::CAND_CAP);
     kcpp_cand_hdr hdr;
-    if (kcpp_model_candidates(e.stages.back(), kcand::CAND_K, e.f_set.data(), (int)e.f_set.size(), e.f_add.data(),
-                              (int)e.f_add.size(), e.f_sub.data(), (int)e.f_sub.size(), &hdr, e.f_ids.data(), e.f_vals.data(),
-                              kcand::CAND_CAP))
+    kcpp_cand_hdr_masked hm;
+    if (mask) {
+        if (kcpp_model_candidates_masked(e.stages.back(), kcand::CAND_K, e.f_set.data(), (int)e.f_set.size(), e.f_add.data(),
+                                         (int)e.f_add.size(), e.f_sub.data(), (int)e.f_sub.size(), mask, &hm, e.f_ids.data(),
+                                         e.f_vals.data(), kcand::CAND_CAP))
+            return -1;
+        hdr = hm.h;
+    } else if (kcpp_model_candidates(e.stages.back(), kcand::CAND_K, e.f_set.data(), (int)e.f_set.size(), e.f_add.data(),
+                                     (int)e.f_add.size(), e.f_sub.data(), (int)e.f_sub.size(), &hdr, e.f_ids.data(),
+                                     e.f_vals.data(), kcand::CAND_CAP)) {
         return -1;
+    }
     if (hdr.n_bad > 0) { ++g_front_stats[1]; return 0; }
     if (hdr.nhave > kcand::CAND_CAP) { ++g_front_stats[2]; return 0; }
     kcand::Hdr h;
     memcpy(&h, &hdr, sizeof(h));
-    if (!kcand::top_k_from_survivors(h, e.f_ids.data(), e.f_vals.data(), hdr.nhave, nv, kcand::CAND_K, e.f_cand)) {
+    if (mask && hdr.ib == 0) {
+        if (!kcand::rebuild_masked(h, hm.n_rej, mask, e.f_ids.data(), e.f_vals.data(), hdr.nhave, nv, e.f_cand)) {
+            ++g_front_stats[3];
+            return 0;
+        }
+        ksamp::Cands c{e.f_cand.data(), e.f_cand.size(), false};
+        ksamp::top_k(&c, kcand::CAND_K);
+        e.f_cand.resize(c.size);
+        ++g_gram_stats[3];
+    } else if (!kcand::top_k_from_survivors(h, e.f_ids.data(), e.f_vals.data(), hdr.nhave, nv, kcand::CAND_K, e.f_cand)) {
         ++g_front_stats[3];
         return 0;
+    } else if (mask) {
+        ++g_gram_stats[5];
     }
     ++g_front_stats[0];
     *tok = ksamp::sample_candidates(e.f_cand, S.n_ctx, nv, P, last_n, rng, mu);
     return 1;
+}
+
+// the grammar's reject mask of this step, built once (e.g_mask, e.g_nrej); false when a limit of grammar.h was hit
+bool grammar_mask(Engine &e) {
+    if (e.g_nrej >= 0) return true;
+    const int nv = e.hp.n_vocab;
+    if ((int)e.g_pieces.size() != nv) {        // once per loaded model
+        e.g_pieces.resize(nv), e.g_ptr.resize(nv), e.g_len.resize(nv);
+        for (int i = 0; i < nv; ++i) e.g_pieces[i] = e.tok.piece(i);
+        for (int i = 0; i < nv; ++i) e.g_ptr[i] = e.g_pieces[i].data(), e.g_len[i] = e.g_pieces[i].size();
+        e.g_vocab.build(nv, [&](int i) -> const std::string & { return e.g_pieces[i]; });
+    }
+    e.g_mask.resize(kcand::mask_words(nv));
+    const auto t0 = std::chrono::steady_clock::now();
+    e.g_nrej = kgram::reject_mask(g_gram, e.g_vocab, e.g_ptr.data(), e.g_len.data(), nv, e.tok.eos(), e.tok.eot(), true, e.g_work,
+                                  e.g_mask.data());
+    g_gram_mask_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return e.g_nrej >= 0;
+}
+// does the grammar take token t now: sample_grammar's rules for the one candidate
+bool grammar_allows(Engine &e, int t) {
+    if (t == e.tok.eos() || (t == e.tok.eot() && t != -1)) return kgram::allows_end(g_gram);
+    const std::string p = e.tok.piece(t);
+    if (p.empty() || p[0] == 0) return false;
+    std::vector<uint32_t> cps;
+    kgram::Partial end;
+    kgram::decode_utf8(p.data(), p.size(), g_gram.partial, cps, &end);
+    const std::vector<kgram::Cand> one{kgram::Cand{(uint32_t)t, cps.data(), end}};
+    std::vector<kgram::Cand> rej;
+    kgram::Guard gd;
+    kgram::reject_candidates(g_gram.rules, g_gram.stacks, one, rej, &gd);
+    return rej.empty() && !gd.overflow;
 }
 
 // one sampled token from the last stage's logits (gpttype_adapter.cpp:3182-3232); < 0 on a device error.
@@ -636,22 +707,48 @@ int sample(Engine &e, const SamplerSetup &S, const std::vector<int> &last_n, std
            const std::vector<int> *slop, bool *on_dev) {
     kcpp_model *last = e.stages.back();
     const int eos = e.tok.eos(), eot = e.tok.eot();
+    const bool gram = g_gram.active();
     *on_dev = false;
+    e.g_nrej = -1;
+    if (gram) ++g_gram_stats[0];
     if (chain_is_argmax(S) && !slop) {
         int32_t t = 0;
         // after a single-token step the step's own argmax is already on the device: read it; after a prefill, run it
         if (e.dev_tok ? kcpp_model_read_argmax(last, &t) : kcpp_model_argmax(last, &t)) return -1;
-        if (!(S.suppress_eos && (t == eos || (t == eot && eot != -1)))) {
-            *on_dev = true;
-            return t;
+        const auto is_end = [&](int x) { return x == eos || (x == eot && eot != -1); };
+        if (!(S.suppress_eos && is_end(t))) {
+            // With a grammar the chain's token is the argmax over the tokens the grammar allows (the rejected ones are
+            // -inf).  If the unmasked argmax is allowed it IS that masked argmax: no allowed logit is greater, and among
+            // equal logits it has the lowest id of all, so also of the allowed ones.  Only one token has to be tested.
+            if (!gram || grammar_allows(e, t)) {
+                if (gram) ++g_gram_stats[1];
+                *on_dev = true;
+                return t;
+            }
+            // rejected: the argmax over the allowed ids, same merge order so the same tie rule; the token then goes to
+            // stage 0 from the host like a sampled one.  No allowed token, a best logit that is not finite, or a
+            // suppressed EOS on top: the host chain decides.
+            int32_t tm = -1;
+            float lm = 0.0f;
+            if (grammar_mask(e) && e.g_nrej < e.hp.n_vocab && last && kcpp_model_argmax_masked(last, e.g_mask.data(), &tm, &lm) == 0 &&
+                tm >= 0 && std::isfinite(lm) && !(S.suppress_eos && is_end(tm))) {
+                ++g_gram_stats[2];
+                return tm;
+            }
         }
+    }
+    const uint32_t *mask = nullptr;
+    if (gram) {
+        if (!grammar_mask(e)) { kcpp_set_last_error("grammar: the stack set outgrew its limit"); return -1; }
+        mask = e.g_mask.data();
     }
     // at or below 5000 every candidate survives: nothing to gain
     if (S.front && e.hp.n_vocab > kcand::CAND_K && e.hp.n_vocab <= kcand::CAND_MAX_N) {
         int t = 0;
-        const int r = sample_front(e, S, last_n, rng, mu, slop, &t);
+        const int r = sample_front(e, S, last_n, rng, mu, slop, mask, &t);
         if (r) return r < 0 ? -1 : t;
     }
+    if (gram) ++g_gram_stats[4];
     e.logits.resize(e.hp.n_vocab);
     if (kcpp_model_read_logits(last, e.logits.data())) return -1;
     float *l = e.logits.data();
@@ -663,7 +760,8 @@ int sample(Engine &e, const SamplerSetup &S, const std::vector<int> &last_n, std
     if (slop)
         for (int b : *slop)
             if (b >= 0 && b < e.hp.n_vocab) l[b] = low;
-    return ksamp::sample_logits(l, S.n_ctx, e.hp.n_vocab, S.P, S.biases, S.restarts, e.ctx, last_n, rng, mu);
+    // the grammar's -inf lands inside the chain, after the biases and before DRY, where sample_grammar runs
+    return ksamp::sample_logits(l, S.n_ctx, e.hp.n_vocab, S.P, S.biases, S.restarts, e.ctx, last_n, rng, mu, mask);
 }
 
 // ---- context shifting (restatement of model_adapter.cpp:337-430 and gpttype_adapter.cpp:1504-1571)
@@ -1056,6 +1154,17 @@ generation_outputs generate(const generation_inputs in) {
     // SampleLogits' n_ctx is kcpp_data->n_ctx, which generate() sets to the request's max_context_length
     // (gpttype_adapter.cpp:2646, passed as nctx at :3227)
     const SamplerSetup S = make_sampler(*e, in, in.max_context_length > 0 ? in.max_context_length : max_ctx);
+    // load_grammar (gpttype_adapter.cpp:2708-2721, 1460-1482): every request loads its grammar anew, unless it asks to
+    // retain the state and carries the same non-empty text as the last one.  A text that does not parse, refers to an
+    // undefined rule or is left-recursive leaves no grammar: the request runs unconstrained, after a notice.
+    {
+        const std::string gs = in.grammar ? in.grammar : "";
+        if (!(in.grammar_retain_state && !gs.empty() && g_gram.source == gs)) {
+            if (!kgram::load(g_gram, gs.c_str()) && !gs.empty()) fprintf(stderr, "[kcpp] generate: ignored invalid grammar\n");
+        }
+        g_gram.source = gs;
+        g_gram_mask_ms = 0;
+    }
     // SampleLogits' function-static mirostat_mu (:1369) is initialised by the first call that enters the
     // mirostat branch, with that call's tau
     static bool mu_init = false;
@@ -1090,6 +1199,7 @@ generation_outputs generate(const generation_inputs in) {
     };
     g_last_tokens.clear();
     int n_gen = 0, stop = KCPP_STOP_OUT_OF_TOKENS;
+    bool gram_failed = false;
     double tm_sample = 0, tm_step = 0;     // host time in sample() / in the step's enqueue (KCPP_GEN_TIMING diagnostics)
     for (; n_gen < max_len; ++n_gen) {
         if (g_abort) { stop = KCPP_STOP_CUSTOM_STOPPER; break; }
@@ -1098,8 +1208,32 @@ generation_outputs generate(const generation_inputs in) {
         const auto ts0 = std::chrono::steady_clock::now();
         const int t = sample(*e, S, last_n, rng, &g_mirostat_mu, sb == slop.end() ? nullptr : &sb->second, &on_dev);
         tm_sample += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts0).count();
-        if (t < 0) { fprintf(stderr, "[kcpp] generate: sampling failed: %s\n", kcpp_last_error()); break; }
+        if (t < 0) {
+            fprintf(stderr, "[kcpp] generate: sampling failed: %s\n", kcpp_last_error());
+            if (g_gram.overflow) {          // a limit of grammar.h hit while building the mask: status 0, and the state
+                g_gram.clear();             // is not kept for a later grammar_retain_state request
+                g_gram.source.clear();
+                gram_failed = true;
+            }
+            break;
+        }
         g_last_tokens.push_back(t);
+        // grammar_accept_token (:1437-1458) after every drawn token, whichever path drew it; an antislop rewind below
+        // leaves the grammar where it is, as ContextRewind does.  The reference asserts when EOS arrives while no stack
+        // is empty or when no stack takes the token; neither happens while the mask is right: an error, not an abort
+        if (g_gram.active()) {
+            const std::string gp = e->tok.piece(t);
+            const int grc = kgram::accept_piece(g_gram, gp.data(), gp.size(), t == e->tok.eos() || (t == e->tok.eot() && t != -1));
+            if (grc) {
+                kcpp_set_last_error(grc == -1 ? "grammar: end-of-sequence token sampled while the grammar is incomplete"
+                                              : "grammar: the sampled token left no stack");
+                fprintf(stderr, "[kcpp] generate: %s\n", kcpp_last_error());
+                g_gram.clear();
+                g_gram.source.clear();
+                gram_failed = true;
+                break;
+            }
+        }
         if (!last_n.empty()) last_n.erase(last_n.begin());     // (:3238: an antislop rewind may have emptied it)
         last_n.push_back(t);
         const bool eos_tok = t == e->tok.eos() || (t == e->tok.eot() && t != -1);
@@ -1176,8 +1310,8 @@ generation_outputs generate(const generation_inputs in) {
     }
     if (link_errors(*e)) fprintf(stderr, "[kcpp] generate: a linked hand-off timed out; the tokens after it are invalid\n");
     if (getenv("KCPP_GEN_TIMING"))
-        fprintf(stderr, "[kcpp] generate timing: %d tokens, sample %.3f ms/token, step enqueue %.3f ms/token\n", n_gen,
-                tm_sample / std::max(1, n_gen), tm_step / std::max(1, n_gen));
+        fprintf(stderr, "[kcpp] generate timing: %d tokens, sample %.3f ms/token, step enqueue %.3f ms/token, grammar mask %.3f ms/token\n",
+                n_gen, tm_sample / std::max(1, n_gen), tm_step / std::max(1, n_gen), g_gram_mask_ms / std::max(1, n_gen));
     while (!delayed.empty()) {               // flush what the delay line still holds (:3497-3505)
         if (!hit) emit(delayed.front());
         delayed.pop_front();
@@ -1195,8 +1329,8 @@ generation_outputs generate(const generation_inputs in) {
         std::lock_guard<std::mutex> lk(g_out_mtx);
         g_result = g_concat;
     }
-    out.status = 1;
-    out.stopreason = stop;
+    out.status = gram_failed ? 0 : 1;
+    out.stopreason = gram_failed ? KCPP_STOP_INVALID : stop;
     out.text = g_result.c_str();
     g_finished = true;
     return out;
@@ -1410,11 +1544,15 @@ int kcpp_sampler_probe(const float *logits, int n_vocab, int n_ctx, const float 
 // kcand::top_k_from_survivors and the rest of the chain.  *status_out: 0 through the front end; 1 n_bad, 2 more
 // survivors than the capacity, 3 bucket mismatch: the chain then ran from the edited full logits, as generate() falls
 // back.  Same outputs as kcpp_sampler_probe on logits that already carry the edits.
-int kcpp_sampler_probe_front(const float *logits, int n_vocab, int n_ctx, const float *fp, const int *ip, const int *order,
-                             int n_order, const int *ctx_toks, int n_ctx_toks, const int *last_n, int n_last,
-                             const int *restarts, int n_restart_ints, unsigned seed, float *mu, int *out_ids, float *out_p,
-                             int cap, int *out_n, const int *set_ids, int n_set, const int *add_ids, const float *add_v,
-                             int n_add, const int *sub_ids, const float *sub_v, int n_sub, int *status_out) {
+// kcpp_sampler_probe_front_masked: the same under a grammar's reject mask ((n_vocab + 31) / 32 words) -- the masked CPU
+// model, then the bucket tail (status 0) or, with the cut in bucket 0, the rebuilt n_vocab-entry array through
+// ksamp::top_k (status 4); on a fallback the mask goes into the full chain after the biases.  Same outputs as
+// kcpp_sampler_probe on logits that carry the edits and -inf at the rejected ids.
+static int probe_front(const float *logits, int n_vocab, int n_ctx, const float *fp, const int *ip, const int *order,
+                       int n_order, const int *ctx_toks, int n_ctx_toks, const int *last_n, int n_last,
+                       const int *restarts, int n_restart_ints, unsigned seed, float *mu, int *out_ids, float *out_p,
+                       int cap, int *out_n, const int *set_ids, int n_set, const int *add_ids, const float *add_v,
+                       int n_add, const int *sub_ids, const float *sub_v, int n_sub, const uint32_t *mask, int *status_out) {
     if (!logits || n_vocab <= 0 || !fp || !ip || n_set < 0 || n_add < 0 || n_sub < 0) return -1;
     ksamp::Params P;
     ksamp::RestartSeqs rs;
@@ -1431,14 +1569,27 @@ int kcpp_sampler_probe_front(const float *logits, int n_vocab, int n_ctx, const 
     kcand::Hdr hdr;
     std::vector<int32_t> ids;
     std::vector<float> vals;
-    if (kcand::cand_front_ref(logits, n_vocab, kcand::CAND_K, setv.data(), n_set, adds.data(), n_add, subs.data(),
-                              (int)subs.size(), &hdr, ids, vals, kcand::CAND_CAP))
+    int32_t n_rej = 0;
+    if (kcand::cand_front_ref_masked(logits, n_vocab, kcand::CAND_K, setv.data(), n_set, adds.data(), n_add, subs.data(),
+                                     (int)subs.size(), mask, &hdr, &n_rej, ids, vals, kcand::CAND_CAP))
         return -1;
     std::vector<ksamp::TokData> cand;
     int status = hdr.n_bad > 0 ? 1 : (hdr.nhave > kcand::CAND_CAP ? 2 : 0);
-    if (!status && !kcand::top_k_from_survivors(hdr, ids.data(), vals.data(), (int)ids.size(), n_vocab, kcand::CAND_K, cand))
+    if (!status && mask && hdr.ib == 0) {
+        if (kcand::rebuild_masked(hdr, n_rej, mask, ids.data(), vals.data(), (int)ids.size(), n_vocab, cand)) {
+            ksamp::Cands c5{cand.data(), cand.size(), false};
+            ksamp::top_k(&c5, kcand::CAND_K);
+            cand.resize(c5.size);
+            status = 4;
+        } else {
+            status = 3;
+        }
+    } else if (!status &&
+               !kcand::top_k_from_survivors(hdr, ids.data(), vals.data(), (int)ids.size(), n_vocab, kcand::CAND_K, cand)) {
         status = 3;
+    }
     if (status_out) *status_out = status;
+    if (status == 4) status = 0;
     const bool miro = P.mirostat == 1 || P.mirostat == 2;
     std::mt19937 rng(seed);
     float mu2 = *mu;
@@ -1453,11 +1604,11 @@ int kcpp_sampler_probe_front(const float *logits, int n_vocab, int n_ctx, const 
         for (size_t i = 0; i < n_sub_given; ++i) l[subs[i].id] -= subs[i].v;
     }
     if (miro) {
-        tok = status ? ksamp::sample_logits(l.data(), n_ctx, n_vocab, P, {}, rs, ctxv, lastv, rng, &mu2)
+        tok = status ? ksamp::sample_logits(l.data(), n_ctx, n_vocab, P, {}, rs, ctxv, lastv, rng, &mu2, mask)
                      : ksamp::sample_candidates(cand, n_ctx, n_vocab, P, lastv, rng, &mu2);
         *mu = mu2;
     } else {
-        c = status ? ksamp::apply_chain(cand, l.data(), n_ctx, n_vocab, P, {}, rs, ctxv, lastv, rng, false)
+        c = status ? ksamp::apply_chain(cand, l.data(), n_ctx, n_vocab, P, {}, rs, ctxv, lastv, rng, false, mask)
                    : ksamp::apply_order(ksamp::Cands{cand.data(), cand.size(), true}, n_ctx, P, lastv, rng, false);
         std::vector<ksamp::TokData> keep(c.data, c.data + c.size);
         ksamp::Cands ck{keep.data(), keep.size(), c.sorted};
@@ -1470,6 +1621,27 @@ int kcpp_sampler_probe_front(const float *logits, int n_vocab, int n_ctx, const 
     return tok;
 }
 
+int kcpp_sampler_probe_front(const float *logits, int n_vocab, int n_ctx, const float *fp, const int *ip, const int *order,
+                             int n_order, const int *ctx_toks, int n_ctx_toks, const int *last_n, int n_last,
+                             const int *restarts, int n_restart_ints, unsigned seed, float *mu, int *out_ids, float *out_p,
+                             int cap, int *out_n, const int *set_ids, int n_set, const int *add_ids, const float *add_v,
+                             int n_add, const int *sub_ids, const float *sub_v, int n_sub, int *status_out) {
+    return probe_front(logits, n_vocab, n_ctx, fp, ip, order, n_order, ctx_toks, n_ctx_toks, last_n, n_last, restarts,
+                       n_restart_ints, seed, mu, out_ids, out_p, cap, out_n, set_ids, n_set, add_ids, add_v, n_add, sub_ids,
+                       sub_v, n_sub, nullptr, status_out);
+}
+int kcpp_sampler_probe_front_masked(const float *logits, int n_vocab, int n_ctx, const float *fp, const int *ip,
+                                    const int *order, int n_order, const int *ctx_toks, int n_ctx_toks, const int *last_n,
+                                    int n_last, const int *restarts, int n_restart_ints, unsigned seed, float *mu, int *out_ids,
+                                    float *out_p, int cap, int *out_n, const int *set_ids, int n_set, const int *add_ids,
+                                    const float *add_v, int n_add, const int *sub_ids, const float *sub_v, int n_sub,
+                                    const uint32_t *mask, int *status_out) {
+    if (!mask) return -1;
+    return probe_front(logits, n_vocab, n_ctx, fp, ip, order, n_order, ctx_toks, n_ctx_toks, last_n, n_last, restarts,
+                       n_restart_ints, seed, mu, out_ids, out_p, cap, out_n, set_ids, n_set, add_ids, add_v, n_add, sub_ids,
+                       sub_v, n_sub, mask, status_out);
+}
+
 // the sampling front end's switch for the generate() calls that follow: 1 on, 0 off, -1 the environment's answer
 // (KCPP_SAMPLE_DEV, read per call; unset: on)
 void kcpp_expose_set_sample_front(int on) { g_front_override = on < 0 ? -1 : (on != 0); }
@@ -1478,6 +1650,66 @@ void kcpp_expose_set_sample_front(int on) { g_front_override = on < 0 ? -1 : (on
 void kcpp_expose_sample_front_stats(int64_t out[4]) {
     for (int i = 0; i < 4; ++i) { out[i] = g_front_stats[i]; g_front_stats[i] = 0; }
 }
+// out = {steps with a grammar, greedy tokens the grammar took without a mask, masked argmax runs, sampled tokens rebuilt
+// from every allowed candidate (the cut in bucket 0), full-read fallbacks under a grammar, sampled tokens through the
+// bucket tail under a grammar} since the last call; reading resets them
+void kcpp_expose_grammar_stats(int64_t out[6]) {
+    for (int i = 0; i < 6; ++i) { out[i] = g_gram_stats[i]; g_gram_stats[i] = 0; }
+}
+// host milliseconds spent building reject masks during the last generate()
+double kcpp_expose_grammar_mask_ms(void) { return g_gram_mask_ms; }
+
+// ---- test hooks for grammar.h (tests/test_grammar.py), host only
+struct kcpp_grammar { kgram::Grammar g; };
+// the grammar of a GBNF text, or null when the text gives no grammar (a syntax error, an undefined rule, left recursion)
+kcpp_grammar *kcpp_grammar_create(const char *text) {
+    kcpp_grammar *h = new kcpp_grammar;
+    if (!kgram::load(h->g, text)) { delete h; return nullptr; }
+    return h;
+}
+void kcpp_grammar_free(kcpp_grammar *h) { delete h; }
+// the element arrays: per rule its (type, value) pairs, END included, rule after rule; rule_len[r] = elements of rule r.
+// Returns the rule count (at most cap_rules lengths and cap_elems pairs written; *n_elems = the pairs there are)
+int kcpp_grammar_rules(const kcpp_grammar *h, uint32_t *elems, int cap_elems, int32_t *rule_len, int cap_rules, int *n_elems) {
+    if (!h) return -1;
+    int at = 0;
+    for (size_t r = 0; r < h->g.rules.size(); ++r) {
+        if ((int)r < cap_rules) rule_len[r] = (int32_t)h->g.rules[r].size();
+        for (const kgram::Elem &el : h->g.rules[r]) {
+            if (at < cap_elems) { elems[2 * at] = el.type; elems[2 * at + 1] = el.value; }
+            ++at;
+        }
+    }
+    if (n_elems) *n_elems = at;
+    return (int)h->g.rules.size();
+}
+int kcpp_grammar_n_stacks(const kcpp_grammar *h) { return h ? (int)h->g.stacks.size() : -1; }
+// sample_grammar over a vocabulary of n pieces (piece i = blob[off[i] .. off[i + 1])): mask_out = (n + 31) / 32 words,
+// bit set = rejected.  use_cache != 0: from the vocabulary decoded once (used while no character is carried over),
+// else every piece decoded with the carried state.  Returns the rejected count, or a negative code.
+int kcpp_grammar_reject(kcpp_grammar *h, const uint8_t *blob, const int64_t *off, int n, int eos, int eot, int use_cache,
+                        uint32_t *mask_out) {
+    if (!h || !blob || !off || n < 1 || !mask_out) return -1;
+    std::vector<const char *> ptr(n);
+    std::vector<size_t> len(n);
+    for (int i = 0; i < n; ++i) ptr[i] = (const char *)blob + off[i], len[i] = (size_t)(off[i + 1] - off[i]);
+    kgram::VocabCache vc;
+    if (use_cache) vc.build(n, [&](int i) { return std::string(ptr[i], len[i]); });
+    kgram::MaskWork w;
+    return kgram::reject_mask(h->g, vc, ptr.data(), len.data(), n, eos, eot, use_cache != 0, w, mask_out);
+}
+// grammar_accept_token for one piece (is_eos: the EOS / EOT rule instead): 0; -1 EOS while no stack is empty; -2 no
+// stack took the piece
+int kcpp_grammar_accept_piece(kcpp_grammar *h, const uint8_t *piece, int len, int is_eos) {
+    if (!h || len < 0 || (!piece && len > 0)) return -3;
+    return kgram::accept_piece(h->g, (const char *)piece, (size_t)len, is_eos != 0);
+}
+// the carried UTF-8 state: out = {value, n_remain}
+void kcpp_grammar_partial(const kcpp_grammar *h, int64_t out[2]) {
+    out[0] = h ? (int64_t)h->g.partial.value : 0;
+    out[1] = h ? (int64_t)h->g.partial.n_remain : 0;
+}
+
 // SampleLogits' mirostat_mu lives as long as the process (the reference's function-static): a test that runs one
 // mirostat request twice sets it back in between.  set != 0: mu = value; returns the current mu
 float kcpp_expose_mirostat_mu(int set, float value) {

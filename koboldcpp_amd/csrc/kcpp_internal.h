@@ -25,6 +25,7 @@ int kcpp_dequantize(int type, const void *w, float *y, int64_t K, int64_t N, voi
 int kcpp_quantize_act(int vtype, const float *x, int64_t ldx, void *out, int64_t K, int64_t M, void *stream);
 int64_t kcpp_act_bytes(int wtype, int64_t K, int64_t M);
 int kcpp_vec_dot_type(int wtype);
+void kcpp_set_last_error(const char *msg);      // what kcpp_last_error() returns next (runtime.cpp)
 }
 #include "../../include/kcpp_mi355x.h"
 #include <hip/hip_runtime.h>

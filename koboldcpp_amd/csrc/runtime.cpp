@@ -33,6 +33,7 @@
 
 static thread_local std::string g_err;
 extern "C" const char *kcpp_last_error(void) { return g_err.c_str(); }
+void kcpp_set_last_error(const char *msg) { g_err = msg ? msg : ""; }      // for expose.cpp (kcpp_internal.h)
 
 #define RT_CHECK(expr)                                                                                 \
     do {                                                                                               \
@@ -737,7 +738,8 @@ struct CandCtx {
     kcand::WsLayout w{};
     uint8_t *ws = nullptr;               // device workspace (kcand::ws_layout)
     kcand::Op *ops_pin = nullptr;        // pinned staging of the edit program
-    uint8_t *out_pin = nullptr;          // pinned: Hdr, then cap Pairs
+    uint8_t *out_pin = nullptr;          // pinned: Hdr (with a mask: HdrM), then cap Pairs
+    uint32_t *mask_pin = nullptr;        // pinned staging of the reject mask, (n_max + 31) / 32 words
     std::vector<uint64_t> keys;
 };
 static void cand_free(CandCtx *c) {
@@ -745,6 +747,7 @@ static void cand_free(CandCtx *c) {
     if (c->ws) hipFree(c->ws);
     if (c->ops_pin) hipHostFree(c->ops_pin);
     if (c->out_pin) hipHostFree(c->out_pin);
+    if (c->mask_pin) hipHostFree(c->mask_pin);
     delete c;
 }
 static CandCtx *cand_create(int n, int cap, int64_t max_ops) {
@@ -759,7 +762,11 @@ static CandCtx *cand_create(int n, int cap, int64_t max_ops) {
     }
     if (e == hipSuccess) {
         what = "result staging";
-        e = hipHostMalloc((void **)&c->out_pin, sizeof(kcand::Hdr) + (size_t)cap * sizeof(kcand::Pair), hipHostMallocDefault);
+        e = hipHostMalloc((void **)&c->out_pin, sizeof(kcand::HdrM) + (size_t)cap * sizeof(kcand::Pair), hipHostMallocDefault);
+    }
+    if (e == hipSuccess) {
+        what = "mask staging";
+        e = hipHostMalloc((void **)&c->mask_pin, kcand::mask_words(n) * 4, hipHostMallocDefault);
     }
     if (e != hipSuccess) {
         g_err = std::string("candidates: ") + what + " alloc: " + hipGetErrorString(e);
@@ -769,10 +776,12 @@ static CandCtx *cand_create(int n, int cap, int64_t max_ops) {
     return c;
 }
 static_assert(sizeof(kcpp_cand_hdr) == sizeof(kcand::Hdr) && sizeof(kcpp_cand_edit) == sizeof(kcand::Edit), "cand ABI");
-// edits up, the passes, results back: one stream synchronisation while nhave <= CAND_FIRST
+static_assert(sizeof(kcpp_cand_hdr_masked) == sizeof(kcand::HdrM) && sizeof(kcand::HdrM) % 8 == 0, "cand ABI (masked)");
+// edits (and the reject mask, when given) up, the passes, results back: one stream synchronisation while
+// nhave <= CAND_FIRST.  mask: null, or (n + 31) / 32 host words; *n_rej_out its count
 static int cand_run(CandCtx *c, const float *logits_dev, int n, int k, const int32_t *set_ids, int n_set,
-                    const kcpp_cand_edit *adds, int n_add, const kcpp_cand_edit *subs, int n_sub, kcpp_cand_hdr *hdr_out,
-                    int32_t *ids_out, float *logits_out, int cap, hipStream_t s) {
+                    const kcpp_cand_edit *adds, int n_add, const kcpp_cand_edit *subs, int n_sub, const uint32_t *mask,
+                    kcpp_cand_hdr *hdr_out, int32_t *n_rej_out, int32_t *ids_out, float *logits_out, int cap, hipStream_t s) {
     kcand::Plan p;
     if (!c || !logits_dev || !hdr_out || n > c->n_max || kcand::plan(n, &p)) { g_err = "candidates: n out of range"; return -2; }
     if (cap < 0 || cap > c->cap || (cap > 0 && (!ids_out || !logits_out))) { g_err = "candidates: bad capacity"; return -2; }
@@ -792,26 +801,36 @@ static int cand_run(CandCtx *c, const float *logits_dev, int n, int k, const int
     a.scratch = (float *)(ws + c->w.scratch), a.minpart = (float *)(ws + c->w.minpart), a.low = (float *)(ws + c->w.low);
     a.hist = (int32_t *)(ws + c->w.hist), a.bad = (int32_t *)(ws + c->w.bad), a.off = (int32_t *)(ws + c->w.off);
     a.out = ws + c->w.out;
+    const size_t hdr_bytes = mask ? sizeof(kcand::HdrM) : sizeof(kcand::Hdr);
+    if (mask) {
+        const size_t nw = kcand::mask_words(n);
+        memcpy(c->mask_pin, mask, nw * 4);
+        if (n & 31) c->mask_pin[nw - 1] &= (1u << (n & 31)) - 1;       // bits past n - 1 say nothing
+        RT_CHECK(hipMemcpyAsync(ws + c->w.mask, c->mask_pin, nw * 4, hipMemcpyHostToDevice, s));
+        a.mask = (const uint32_t *)(ws + c->w.mask), a.rej = (int32_t *)(ws + c->w.rej);
+    }
     if (int rc = kcpp_cand_launch(p, a, s)) { g_err = "candidates: launch failed"; return rc; }
     const int first = std::min(cap, kcand::CAND_FIRST);
-    RT_CHECK(hipMemcpyAsync(c->out_pin, a.out, sizeof(kcand::Hdr) + (size_t)first * sizeof(kcand::Pair), hipMemcpyDeviceToHost, s));
+    RT_CHECK(hipMemcpyAsync(c->out_pin, a.out, hdr_bytes + (size_t)first * sizeof(kcand::Pair), hipMemcpyDeviceToHost, s));
     RT_CHECK(hipStreamSynchronize(s));
     memcpy(hdr_out, c->out_pin, sizeof(kcand::Hdr));
+    if (mask && n_rej_out) *n_rej_out = ((const kcand::HdrM *)c->out_pin)->n_rej;
     const int have = std::max(0, std::min(hdr_out->nhave, cap));
     if (have > first) {
-        const size_t at = sizeof(kcand::Hdr) + (size_t)first * sizeof(kcand::Pair);
+        const size_t at = hdr_bytes + (size_t)first * sizeof(kcand::Pair);
         RT_CHECK(hipMemcpyAsync(c->out_pin + at, (const uint8_t *)a.out + at, (size_t)(have - first) * sizeof(kcand::Pair),
                                 hipMemcpyDeviceToHost, s));
         RT_CHECK(hipStreamSynchronize(s));
     }
-    const kcand::Pair *pr = (const kcand::Pair *)(c->out_pin + sizeof(kcand::Hdr));
+    const kcand::Pair *pr = (const kcand::Pair *)(c->out_pin + hdr_bytes);
     for (int i = 0; i < have; ++i) { ids_out[i] = pr[i].id; logits_out[i] = pr[i].v; }
     return 0;
 }
 
-extern "C" int kcpp_logit_candidates(const float *logits_dev, int n, int k, const int32_t *set_ids, int n_set,
-                                     const kcpp_cand_edit *adds, int n_add, const kcpp_cand_edit *subs, int n_sub,
-                                     kcpp_cand_hdr *hdr_out, int32_t *ids_out, float *logits_out, int cap, void *stream) {
+static int logit_candidates(const float *logits_dev, int n, int k, const int32_t *set_ids, int n_set,
+                            const kcpp_cand_edit *adds, int n_add, const kcpp_cand_edit *subs, int n_sub, const uint32_t *mask,
+                            kcpp_cand_hdr *hdr_out, int32_t *n_rej_out, int32_t *ids_out, float *logits_out, int cap,
+                            void *stream) {
     kcand::Plan p;
     if (kcand::plan(n, &p) || cap < 0 || cap > kcand::CAND_CAP || n_set < 0 || n_add < 0 || n_sub < 0) {
         g_err = "candidates: n, cap or list length out of range";
@@ -819,19 +838,44 @@ extern "C" int kcpp_logit_candidates(const float *logits_dev, int n, int k, cons
     }
     CandCtx *c = cand_create(n, cap, (int64_t)n_set + n_add + n_sub);
     if (!c) return -1;
-    const int rc = cand_run(c, logits_dev, n, k, set_ids, n_set, adds, n_add, subs, n_sub, hdr_out, ids_out, logits_out, cap,
-                            (hipStream_t)stream);
+    const int rc = cand_run(c, logits_dev, n, k, set_ids, n_set, adds, n_add, subs, n_sub, mask, hdr_out, n_rej_out, ids_out,
+                            logits_out, cap, (hipStream_t)stream);
     if (rc) (void)hipStreamSynchronize((hipStream_t)stream);       // nothing may still read the workspace
     cand_free(c);
     return rc;
+}
+extern "C" int kcpp_logit_candidates(const float *logits_dev, int n, int k, const int32_t *set_ids, int n_set,
+                                     const kcpp_cand_edit *adds, int n_add, const kcpp_cand_edit *subs, int n_sub,
+                                     kcpp_cand_hdr *hdr_out, int32_t *ids_out, float *logits_out, int cap, void *stream) {
+    return logit_candidates(logits_dev, n, k, set_ids, n_set, adds, n_add, subs, n_sub, nullptr, hdr_out, nullptr, ids_out,
+                            logits_out, cap, stream);
+}
+extern "C" int kcpp_logit_candidates_masked(const float *logits_dev, int n, int k, const int32_t *set_ids, int n_set,
+                                            const kcpp_cand_edit *adds, int n_add, const kcpp_cand_edit *subs, int n_sub,
+                                            const uint32_t *mask, kcpp_cand_hdr_masked *hdr_out, int32_t *ids_out,
+                                            float *logits_out, int cap, void *stream) {
+    if (!mask || !hdr_out) { g_err = "candidates: no mask"; return -2; }
+    hdr_out->n_rej = 0, hdr_out->pad = 0;
+    return logit_candidates(logits_dev, n, k, set_ids, n_set, adds, n_add, subs, n_sub, mask, &hdr_out->h, &hdr_out->n_rej,
+                            ids_out, logits_out, cap, stream);
 }
 extern "C" int kcpp_model_candidates(kcpp_model *m, int k, const int32_t *set_ids, int n_set, const kcpp_cand_edit *adds,
                                      int n_add, const kcpp_cand_edit *subs, int n_sub, kcpp_cand_hdr *hdr_out, int32_t *ids_out,
                                      float *logits_out, int cap) {
     if (!m || !m->has_output || !m->cand) { g_err = "candidates: stage has no output head"; return -2; }
     RT_CHECK(hipSetDevice(m->device));
-    return cand_run(m->cand, m->logits, m->hp.n_vocab, k, set_ids, n_set, adds, n_add, subs, n_sub, hdr_out, ids_out,
-                    logits_out, cap, m->stream);
+    return cand_run(m->cand, m->logits, m->hp.n_vocab, k, set_ids, n_set, adds, n_add, subs, n_sub, nullptr, hdr_out, nullptr,
+                    ids_out, logits_out, cap, m->stream);
+}
+extern "C" int kcpp_model_candidates_masked(kcpp_model *m, int k, const int32_t *set_ids, int n_set, const kcpp_cand_edit *adds,
+                                            int n_add, const kcpp_cand_edit *subs, int n_sub, const uint32_t *mask,
+                                            kcpp_cand_hdr_masked *hdr_out, int32_t *ids_out, float *logits_out, int cap) {
+    if (!m || !m->has_output || !m->cand) { g_err = "candidates: stage has no output head"; return -2; }
+    if (!mask || !hdr_out) { g_err = "candidates: no mask"; return -2; }
+    RT_CHECK(hipSetDevice(m->device));
+    hdr_out->n_rej = 0, hdr_out->pad = 0;
+    return cand_run(m->cand, m->logits, m->hp.n_vocab, k, set_ids, n_set, adds, n_add, subs, n_sub, mask, &hdr_out->h,
+                    &hdr_out->n_rej, ids_out, logits_out, cap, m->stream);
 }
 extern "C" int kcpp_cand_plan(int64_t n, int32_t out[4]) {
     kcand::Plan p;
@@ -839,9 +883,9 @@ extern "C" int kcpp_cand_plan(int64_t n, int32_t out[4]) {
     out[0] = p.rc, out[1] = p.slice, out[2] = p.block, out[3] = p.nblk;
     return rc;
 }
-extern "C" int kcpp_cand_front_ref(const float *logits, int n, int k, const int32_t *set_ids, int n_set,
-                                   const kcpp_cand_edit *adds, int n_add, const kcpp_cand_edit *subs, int n_sub,
-                                   kcpp_cand_hdr *hdr_out, int32_t *ids_out, float *logits_out, int cap) {
+static int front_ref(const float *logits, int n, int k, const int32_t *set_ids, int n_set, const kcpp_cand_edit *adds,
+                     int n_add, const kcpp_cand_edit *subs, int n_sub, const uint32_t *mask, kcpp_cand_hdr *hdr_out,
+                     int32_t *n_rej_out, int32_t *ids_out, float *logits_out, int cap) {
     if (!logits || !hdr_out || cap < 0 || (cap > 0 && (!ids_out || !logits_out)) || n_set < 0 || n_add < 0 || n_sub < 0) {
         g_err = "cand_front_ref: bad arguments";
         return -2;
@@ -849,12 +893,26 @@ extern "C" int kcpp_cand_front_ref(const float *logits, int n, int k, const int3
     std::vector<int32_t> ids;
     std::vector<float> vals;
     kcand::Hdr h;
-    const int rc = kcand::cand_front_ref(logits, n, k, set_ids, n_set, (const kcand::Edit *)adds, n_add, (const kcand::Edit *)subs,
-                                         n_sub, &h, ids, vals, cap);
+    const int rc = kcand::cand_front_ref_masked(logits, n, k, set_ids, n_set, (const kcand::Edit *)adds, n_add,
+                                                (const kcand::Edit *)subs, n_sub, mask, &h, n_rej_out, ids, vals, cap);
     if (rc) { g_err = "cand_front_ref: n or an edit id out of range"; return -2; }
     memcpy(hdr_out, &h, sizeof(h));
     for (size_t i = 0; i < ids.size(); ++i) { ids_out[i] = ids[i]; logits_out[i] = vals[i]; }
     return 0;
+}
+extern "C" int kcpp_cand_front_ref(const float *logits, int n, int k, const int32_t *set_ids, int n_set,
+                                   const kcpp_cand_edit *adds, int n_add, const kcpp_cand_edit *subs, int n_sub,
+                                   kcpp_cand_hdr *hdr_out, int32_t *ids_out, float *logits_out, int cap) {
+    return front_ref(logits, n, k, set_ids, n_set, adds, n_add, subs, n_sub, nullptr, hdr_out, nullptr, ids_out, logits_out, cap);
+}
+extern "C" int kcpp_cand_front_ref_masked(const float *logits, int n, int k, const int32_t *set_ids, int n_set,
+                                          const kcpp_cand_edit *adds, int n_add, const kcpp_cand_edit *subs, int n_sub,
+                                          const uint32_t *mask, kcpp_cand_hdr_masked *hdr_out, int32_t *ids_out,
+                                          float *logits_out, int cap) {
+    if (!mask || !hdr_out) { g_err = "cand_front_ref: no mask"; return -2; }
+    hdr_out->n_rej = 0, hdr_out->pad = 0;
+    return front_ref(logits, n, k, set_ids, n_set, adds, n_add, subs, n_sub, mask, &hdr_out->h, &hdr_out->n_rej, ids_out,
+                     logits_out, cap);
 }
 
 extern "C" int64_t kcpp_model_weight_bytes(kcpp_model *m) { return m->weight_bytes; }
@@ -1927,6 +1985,26 @@ __global__ void __launch_bounds__(256) k_argmax_final(const float2 *__restrict__
         if (pos) { pos[0] += 1; pos[1] += 1; }   // the next single-token step's position and epoch
     }
 }
+// the same two stages over the ids a reject mask allows (bit j % 32 of word j / 32 set: id j is skipped): the same
+// amax_merge order, so the same id among equal logits.  out[0] = the id, or -1 when every id is rejected (or no allowed
+// logit compares: all NaN); out[1] = the bits of its logit.  Writes neither the argmax slot nor the token input.
+__global__ void __launch_bounds__(256) k_argmax_part_masked(const float *__restrict__ x, const uint32_t *__restrict__ mask, int n,
+                                                            float2 *part) {
+    float v = -INFINITY; int i = 0x7fffffff;
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < n; j += ARGMAX_BLOCKS * 256)
+        if (!((mask[j >> 5] >> (j & 31)) & 1u)) amax_merge(v, i, x[j], j);
+    amax_block(v, i);
+    if (threadIdx.x == 0) part[blockIdx.x] = make_float2(v, __int_as_float(i));
+}
+__global__ void __launch_bounds__(256) k_argmax_final_masked(const float2 *__restrict__ part, int32_t *out) {
+    const float2 p = part[threadIdx.x];
+    float v = p.x; int i = __float_as_int(p.y);
+    amax_block(v, i);
+    if (threadIdx.x == 0) {
+        out[0] = i == 0x7fffffff ? -1 : i;
+        out[1] = __float_as_int(v);
+    }
+}
 __global__ void k_pos_step(int32_t *pos) { pos[0] += 1; pos[1] += 1; }
 static int launch_argmax(kcpp_model *m, bool step_pos) {
     hipLaunchKernelGGL(k_argmax_part, dim3(ARGMAX_BLOCKS), dim3(256), 0, m->stream, m->logits, m->hp.n_vocab,
@@ -1974,6 +2052,59 @@ extern "C" int kcpp_model_argmax(kcpp_model *m, int32_t *token_out) {
     RT_CHECK(hipMemcpyAsync(&m->pin[2], m->argmax_dev, 4, hipMemcpyDeviceToHost, m->stream));
     RT_CHECK(hipStreamSynchronize(m->stream));
     *token_out = m->pin[2];
+    return 0;
+}
+
+// argmax over the ids the mask allows (a grammar's reject mask, (n_vocab + 31) / 32 host words), on the stage's logits:
+// *token_out = the id, -1 when no id is allowed; *logit_out (optional) its logit.  The step's own argmax and the token
+// input stay as they are: the caller feeds the token from the host.
+extern "C" int kcpp_model_argmax_masked(kcpp_model *m, const uint32_t *mask_host, int32_t *token_out, float *logit_out) {
+    if (!m || !m->has_output || !m->cand || !mask_host || !token_out) { g_err = "argmax_masked: bad arguments"; return -2; }
+    RT_CHECK(hipSetDevice(m->device));
+    CandCtx *c = m->cand;
+    const int n = m->hp.n_vocab;
+    const size_t nw = kcand::mask_words(n);
+    memcpy(c->mask_pin, mask_host, nw * 4);
+    uint32_t *mask_dev = (uint32_t *)(c->ws + c->w.mask);
+    RT_CHECK(hipMemcpyAsync(mask_dev, c->mask_pin, nw * 4, hipMemcpyHostToDevice, m->stream));
+    hipLaunchKernelGGL(k_argmax_part_masked, dim3(ARGMAX_BLOCKS), dim3(256), 0, m->stream, m->logits, mask_dev, n,
+                       (float2 *)m->argmax_ws);
+    hipLaunchKernelGGL(k_argmax_final_masked, dim3(1), dim3(256), 0, m->stream, (const float2 *)m->argmax_ws, m->argmax_dev + 8);
+    RT_CHECK(hipGetLastError());
+    RT_CHECK(hipMemcpyAsync(&m->pin[8], m->argmax_dev + 8, 8, hipMemcpyDeviceToHost, m->stream));
+    RT_CHECK(hipStreamSynchronize(m->stream));
+    *token_out = m->pin[8];
+    if (logit_out) memcpy(logit_out, &m->pin[9], 4);
+    return 0;
+}
+// the same on any device buffer of n logits (the unit the tests drive): allocates and frees its buffers per call
+extern "C" int kcpp_logit_argmax_masked(const float *logits_dev, int n, const uint32_t *mask_host, int32_t *token_out,
+                                        float *logit_out, void *stream) {
+    if (!logits_dev || n < 1 || !mask_host || !token_out) { g_err = "argmax_masked: bad arguments"; return -2; }
+    hipStream_t s = (hipStream_t)stream;
+    const size_t nw = kcand::mask_words(n);
+    uint8_t *ws = nullptr;
+    RT_CHECK(hipMalloc((void **)&ws, ((nw * 4 + 15) & ~(size_t)15) + 256 * 8 + 16));
+    uint32_t *mask_dev = (uint32_t *)ws;
+    float2 *part = (float2 *)(ws + ((nw * 4 + 15) & ~(size_t)15));
+    int32_t *out = (int32_t *)(part + 256);
+    int32_t res[2] = {-1, 0};
+    const char *what = "mask copy";
+    hipError_t e = hipMemcpy(mask_dev, mask_host, nw * 4, hipMemcpyHostToDevice);      // pageable memory: a blocking copy
+    if (e == hipSuccess) {
+        what = "launch";
+        (void)hipGetLastError();
+        hipLaunchKernelGGL(k_argmax_part_masked, dim3(ARGMAX_BLOCKS), dim3(256), 0, s, logits_dev, (const uint32_t *)mask_dev, n, part);
+        hipLaunchKernelGGL(k_argmax_final_masked, dim3(1), dim3(256), 0, s, (const float2 *)part, out);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) { what = "synchronize"; e = hipStreamSynchronize(s); }
+    if (e == hipSuccess) { what = "result copy"; e = hipMemcpy(res, out, 8, hipMemcpyDeviceToHost); }
+    if (e != hipSuccess) (void)hipStreamSynchronize(s);
+    (void)hipFree(ws);
+    if (e != hipSuccess) { g_err = std::string("argmax_masked: ") + what + ": " + hipGetErrorString(e); return -1; }
+    *token_out = res[0];
+    if (logit_out) memcpy(logit_out, &res[1], 4);
     return 0;
 }
 

@@ -6,8 +6,10 @@
 // and one draw from std::discrete_distribution over mt19937.  Every function below follows the
 // reference function named in its comment, including its sort / tie / min_keep behaviour, so that a
 // given seed draws the same token from the same logits (same libstdc++ distributions).
-// Grammar-constrained sampling is outside SURVEY.md 8 and is not provided.
+// Grammar-constrained sampling: grammar.h computes sample_grammar's rejected tokens as a bitmask; the chain takes it
+// as `reject` and writes -INFINITY where the reference does.
 #pragma once
+#include <stdint.h>
 
 #include <algorithm>
 #include <cfloat>
@@ -453,14 +455,19 @@ inline Cands apply_order(Cands c, int n_ctx, const Params &P, const std::vector<
 
 // the candidate chain of SampleLogits up to (not including) the final draw: biases, DRY, top-5000, then the
 // user's sampler order and XTC.  `cand` holds the candidates; returns the array view.  (mirostat: not here)
+// reject: null, or a grammar's reject bitmask (grammar.h; bit t % 32 of word t / 32): sample_grammar's -INFINITY, written
+// where the reference runs it, after the biases and before DRY (gpttype_adapter.cpp:1349-1365)
 inline Cands apply_chain(std::vector<TokData> &cand, const float *logits, int n_ctx, int n_vocab, const Params &P,
                          const std::vector<LogitBias> &biases, const RestartSeqs &restarts,
                          const std::vector<int> &ctx_tokens, const std::vector<int> &last_n, std::mt19937 &rng,
-                         bool stop_before_order) {
+                         bool stop_before_order, const uint32_t *reject = nullptr) {
     cand.clear();
     cand.reserve(n_vocab);
     for (int t = 0; t < n_vocab; ++t) cand.push_back(TokData{t, logits[t], 0.0f});
     for (const LogitBias &b : biases) cand[b.token_id].logit += b.bias;
+    if (reject)
+        for (int t = 0; t < n_vocab; ++t)
+            if ((reject[t >> 5] >> (t & 31)) & 1u) cand[t].logit = -INFINITY;
     Cands c{cand.data(), cand.size(), false};
     dry(n_ctx, P.dry_penalty_last_n, P.dry_multiplier, P.dry_base, P.dry_allowed_length, restarts, ctx_tokens, &c);
     top_k(&c, 5000);
@@ -479,15 +486,15 @@ inline int sample_tail(Cands c, int n_ctx, int n_vocab, const Params &P, const s
     return draw(&c, rng);
 }
 
-// SampleLogits, gpttype_adapter.cpp:1338-1434 (grammar omitted).  `logits` already carries the EOS /
-// banned-token suppression the caller applies (gpttype_adapter.cpp:3200-3224).  mirostat_mu is the
+// SampleLogits, gpttype_adapter.cpp:1338-1434 (the grammar as its reject mask, see apply_chain).  `logits` already
+// carries the EOS / banned-token suppression the caller applies (gpttype_adapter.cpp:3200-3224).  mirostat_mu is the
 // function-static of the reference (initialised once per process to 2 * tau).
 inline int sample_logits(const float *logits, int n_ctx, int n_vocab, const Params &P, const std::vector<LogitBias> &biases,
                          const RestartSeqs &restarts, const std::vector<int> &ctx_tokens, const std::vector<int> &last_n,
-                         std::mt19937 &rng, float *mirostat_mu) {
+                         std::mt19937 &rng, float *mirostat_mu, const uint32_t *reject = nullptr) {
     std::vector<TokData> cand;
     const bool miro = P.mirostat == 1 || P.mirostat == 2;
-    Cands c = apply_chain(cand, logits, n_ctx, n_vocab, P, biases, restarts, ctx_tokens, last_n, rng, miro);
+    Cands c = apply_chain(cand, logits, n_ctx, n_vocab, P, biases, restarts, ctx_tokens, last_n, rng, miro, reject);
     return sample_tail(c, n_ctx, n_vocab, P, last_n, rng, mirostat_mu);
 }
 

@@ -164,11 +164,27 @@ _SIGS = {
     "kcpp_expose_sample_front_stats": [P],
     "kcpp_expose_last_tokens": [P, I],
     "kcpp_expose_mirostat_mu": [I, Fl],
+    "kcpp_logit_candidates_masked": [P, I, I, P, I, P, I, P, I, P, P, P, P, I, P],
+    "kcpp_model_candidates_masked": [P, I, P, I, P, I, P, I, P, P, P, P, I],
+    "kcpp_cand_front_ref_masked": [P, I, I, P, I, P, I, P, I, P, P, P, P, I],
+    "kcpp_model_argmax_masked": [P, P, P, P],
+    "kcpp_logit_argmax_masked": [P, I, P, P, P, P],
+    "kcpp_expose_grammar_stats": [P],
+    "kcpp_expose_grammar_mask_ms": [],
+    "kcpp_grammar_create": [ctypes.c_char_p],
+    "kcpp_grammar_free": [P],
+    "kcpp_grammar_rules": [P, P, I, P, I, P],
+    "kcpp_grammar_n_stacks": [P],
+    "kcpp_grammar_reject": [P, P, P, I, I, I, I, P],
+    "kcpp_grammar_accept_piece": [P, P, I, I],
+    "kcpp_grammar_partial": [P, P],
 }
 _RES = {"kcpp_gradient_ai_rope_base": Fl, "kcpp_q6p_image_bytes": I64, "kcpp_model_fused_route_count": I64, "kcpp_model_moe_grouped_count": I64, "kcpp_gemm_grouped_ws_bytes": I64, "kcpp_fa_split_ws_bytes": I64, "kcpp_q80t_ws_bytes": I64, "kcpp_act_bytes": I64, "kcpp_fa_ext_workspace_bytes": I64, "kcpp_fa_workspace_bytes": I64, "kcpp_gemm_workspace_bytes": I64,
         "kcpp_model_create": P, "kcpp_model_hidden": P, "kcpp_model_stream": P, "kcpp_model_weight_bytes": I64,
         "kcpp_last_error": ctypes.c_char_p, "kcpp_model_free": None, "kcpp_fa_set_stamps": None,
-        "kcpp_expose_set_sample_front": None, "kcpp_expose_sample_front_stats": None, "kcpp_expose_mirostat_mu": Fl}
+        "kcpp_expose_set_sample_front": None, "kcpp_expose_sample_front_stats": None, "kcpp_expose_mirostat_mu": Fl,
+        "kcpp_expose_grammar_stats": None, "kcpp_expose_grammar_mask_ms": ctypes.c_double, "kcpp_grammar_create": P,
+        "kcpp_grammar_free": None, "kcpp_grammar_partial": None}
 _L.kcpp_act_bytes.argtypes = [I, I64, I64]
 _L.kcpp_kv_cache_bytes.argtypes = [I, I64, I64]
 _L.kcpp_kv_cache_bytes.restype = I64
@@ -589,6 +605,11 @@ class CandHdr(ctypes.Structure):
                 ("hist", ctypes.c_int32 * 128)]
 
 
+class CandHdrMasked(ctypes.Structure):
+    """struct kcpp_cand_hdr_masked: the header of the entries that take a grammar's reject mask"""
+    _fields_ = [("h", CandHdr), ("n_rej", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
 CAND_GUARD_ID, CAND_GUARD_BITS = -77, 0x7FC0DEAD       # what candidates() leaves in entries the call did not write
 
 
@@ -599,21 +620,36 @@ def cand_plan(n):
     return dict(zip(("rc", "slice", "block", "nblk"), out))
 
 
-def candidates(where, logits, k, set_ids=(), adds=(), subs=(), cap=16384, guard=0, stream=None):
+def candidates(where, logits, k, set_ids=(), adds=(), subs=(), cap=16384, guard=0, stream=None, mask=None):
     """The sampling front end on n logits: set_ids set to the lowest logit, adds / subs = [(id, value), ...] added /
     subtracted in list order, then the candidates at or above top_k(k)'s bucket cut.  where: "ref" (the CPU model,
     logits a float32 array), "dev" (kcpp_logit_candidates, logits = (device address, n)) or a Model (its last logits).
+    mask (uint32 words, bit i % 32 of word i / 32 set = id i rejected): the masked entries; the header returned is then
+    a CandHdrMasked (h, n_rej).
     Returns (CandHdr, ids, vals): int32 / float32 arrays of cap + guard entries, min(nhave, cap) of them written and the
     rest left at CAND_GUARD_ID / CAND_GUARD_BITS"""
     import numpy as np
     edit = np.dtype([("id", np.int32), ("v", np.float32)])
     s = np.ascontiguousarray(set_ids, dtype=np.int32)
     a, b = np.array(list(adds), dtype=edit), np.array(list(subs), dtype=edit)
-    hdr = CandHdr()
+    hdr = CandHdr() if mask is None else CandHdrMasked()
     ids = np.full(cap + guard, CAND_GUARD_ID, np.int32)
     vals = np.full(cap + guard, CAND_GUARD_BITS, np.uint32).view(np.float32)
     lists = (s.ctypes.data_as(P), len(s), a.ctypes.data_as(P), len(a), b.ctypes.data_as(P), len(b), ctypes.byref(hdr),
              ids.ctypes.data_as(P), vals.ctypes.data_as(P), int(cap))
+    if mask is not None:
+        mk = np.ascontiguousarray(mask, dtype=np.uint32)
+        lists = lists[:6] + (mk.ctypes.data_as(P),) + lists[6:]
+        if isinstance(where, Model):
+            _chk(_L.kcpp_model_candidates_masked(where.m, int(k), *lists), "model_candidates_masked")
+        elif where == "dev":
+            assert len(mk) == (int(logits[1]) + 31) // 32
+            _chk(_L.kcpp_logit_candidates_masked(logits[0], int(logits[1]), int(k), *lists, stream), "logit_candidates_masked")
+        else:
+            lg = np.ascontiguousarray(logits, dtype=np.float32)
+            assert len(mk) == (len(lg) + 31) // 32
+            _chk(_L.kcpp_cand_front_ref_masked(lg.ctypes.data_as(P), len(lg), int(k), *lists), "cand_front_ref_masked")
+        return hdr, ids, vals
     if isinstance(where, Model):
         _chk(_L.kcpp_model_candidates(where.m, int(k), *lists), "model_candidates")
     elif where == "dev":

@@ -10,7 +10,12 @@ kcpp_expose_synth_weights), a 256-token prompt, then ONE generate() of 256 token
 the on legs drew what the off legs drew.  A library without the front end's hooks (KCPP_LIB pointing at an older build)
 runs the greedy and the off legs only: the baseline the off legs are held to.
 
-  python tools/sample_probe.py [--label NAME] [--out FILE.jsonl] [--prompt 256] [--gen 256]"""
+--grammar FILE puts that GBNF text (tools/json_stream.gbnf: JSON values in an array that never closes, so no request
+ends early) into every request, the warm-up ones included (they also pay the one-time decode of the vocabulary's
+pieces); EOS is allowed in all of them, so a grammar that can finish ends its request.  Each line then also carries the
+grammar counters (kcpp_expose_grammar_stats) and the host milliseconds per token spent on the reject masks.
+
+  python tools/sample_probe.py [--label NAME] [--out FILE.jsonl] [--prompt 256] [--gen 256] [--grammar FILE]"""
 import argparse
 import ctypes
 import json
@@ -27,7 +32,7 @@ import gguf_writer as GW  # noqa: E402
 from koboldcpp_amd import expose as X  # noqa: E402
 
 
-def request(prompt, max_ctx, n, greedy):
+def request(prompt, max_ctx, n, greedy, grammar=b""):
     gi = X.generation_inputs()
     gi.prompt, gi.memory = prompt, b""
     gi.max_context_length, gi.max_length, gi.seed = max_ctx, n, 7
@@ -42,7 +47,8 @@ def request(prompt, max_ctx, n, greedy):
         gi.sampler_order[i] = v
     gi.sampler_len = 7
     # the benchmark bans EOS; the default request allows it (ban_eos_token False)
-    gi.allow_eos_token, gi.bypass_eos_token = (False, False) if greedy else (True, False)
+    gi.allow_eos_token, gi.bypass_eos_token = (False, False) if greedy and not grammar else (True, False)
+    gi.grammar, gi.grammar_retain_state = grammar, False
     return gi
 
 
@@ -53,7 +59,9 @@ def main():
     ap.add_argument("--prompt", type=int, default=256)
     ap.add_argument("--gen", type=int, default=256)
     ap.add_argument("--ubatch", type=int, default=512)
+    ap.add_argument("--grammar", default=None, help="a GBNF file: every request is constrained by it")
     a = ap.parse_args()
+    grammar = open(a.grammar, "rb").read() if a.grammar else b""
     hp, types, max_ctx = dict(bench.LLAMA3_8B), bench.q4_k_m_types(32), a.prompt + a.gen
     lines = []
     with tempfile.TemporaryDirectory() as td:
@@ -71,11 +79,15 @@ def main():
             raise RuntimeError("kcpp_expose_synth_weights failed")
         has_front = hasattr(h, "kcpp_expose_set_sample_front")
         prompt = b" 1" * (a.prompt + 64)                 # koboldcpp.py:4300-4303, cut to --prompt tokens
+        if grammar:
+            h.kcpp_expose_grammar_mask_ms.restype = ctypes.c_double
 
         def leg(name, greedy, front):
             if has_front:
                 h.kcpp_expose_set_sample_front(-1 if front is None else int(front))
-            if h.generate(request(prompt, max_ctx, a.gen, greedy)).status != 1:
+            if grammar:
+                h.kcpp_expose_grammar_stats((ctypes.c_int64 * 6)())
+            if h.generate(request(prompt, max_ctx, a.gen, greedy, grammar)).status != 1:
                 raise RuntimeError("generate failed")
             r = {"label": a.label, "leg": name, "decode_tok_s": round(1000.0 / h.get_last_eval_time(), 2),
                  "ms_per_token": round(h.get_last_eval_time(), 4), "gen_tokens": h.get_last_token_count(),
@@ -85,10 +97,15 @@ def main():
                 h.kcpp_expose_sample_front_stats(stats)
                 r["front_stats"] = list(stats)
                 r["tokens"] = list(toks[:h.kcpp_expose_last_tokens(toks, a.gen)])
+            if grammar:
+                gs = (ctypes.c_int64 * 6)()
+                h.kcpp_expose_grammar_stats(gs)
+                r["grammar_stats"] = list(gs)
+                r["mask_ms_per_token"] = round(h.kcpp_expose_grammar_mask_ms() / max(1, r["gen_tokens"]), 4)
             return r
 
         for g in (True, False):                          # warm-up: first touch, graph capture, both kinds of request
-            h.generate(request(b"hello world", max_ctx, 8, g))
+            h.generate(request(b"hello world", max_ctx, 8, g, grammar))
         if has_front:
             h.kcpp_expose_sample_front_stats((ctypes.c_int64 * 4)())
         lines.append(leg("greedy", True, None))
