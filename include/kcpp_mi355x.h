@@ -302,6 +302,20 @@ int kcpp_moe_route(const float *x, int64_t ldx, const void *w_router, int wtype,
  * n_expert <= 8); -3 when not covered */
 int kcpp_moe_route_norm(const float *x, int64_t ldx, const float *norm_w, float eps, const void *w_router, int wtype,
                         int64_t K, int n_expert, int k, int32_t *ids, float *weights, int T, void *stream);
+/* build_qwen2moe's router (src/llama.cpp:12248-12392): moe_norm_w = 0 leaves the weights the selected softmax
+ * probabilities (llm_build_moe_ffn with norm_w = false; 1 = kcpp_moe_route's bits).  w_gate (null = none; gtype F32,
+ * or F16 with x rounded to f16 first) is the shared expert's gate row [K], dotted with the same input row in the
+ * same launch: gate[t] = silu(z) / z computed as (z / (1 + expf(-z))) / z.  _norm_ex: kcpp_moe_route_norm's limits */
+int kcpp_moe_route_ex(const float *x, int64_t ldx, const void *w_router, int wtype, int64_t K, int n_expert, int k,
+                      int moe_norm_w, const void *w_gate, int gtype, int32_t *ids, float *weights, float *gate, int T,
+                      void *stream);
+int kcpp_moe_route_norm_ex(const float *x, int64_t ldx, const float *norm_w, float eps, const void *w_router, int wtype,
+                           int64_t K, int n_expert, int k, int moe_norm_w, const void *w_gate, int gtype, int32_t *ids,
+                           float *weights, float *gate, int T, void *stream);
+/* x[t][i] = (((slots[0][t][i] + slots[1][t][i]) + ...) + gate[t] * sh[t][i]) + x[t][i] over T rows of E floats
+ * (E and slot_stride multiples of 4): the routed sum, the gated shared expert, the residual, in build_qwen2moe's order */
+int kcpp_moe_combine_shexp(float *x, const float *slots, int64_t slot_stride, int k, const float *gate, const float *sh,
+                           int64_t E, int T, void *stream);
 /* MoE helpers: dst[i] = src[rows[i]] (row gather); dst[rows[i]] = w[i] * src[i] (weighted scatter into
  * the token's top-k slot row); combine: x[i] = ((slots[0][i] + slots[1][i]) + ...) + x[i] over k slots
  * spaced slot_stride floats (the ggml_add chain of llm_build_moe_ffn, src/llama.cpp:9500-9515) */
@@ -413,6 +427,19 @@ typedef struct kcpp_model kcpp_model;
  * slices, synthetic tid = index * 256 + expert) and ffn_gate_inp is the F16/F32 router. */
 kcpp_model *kcpp_model_create(const kcpp_hparams *hp, const int *types, int device, int il0, int il1, int has_embed,
                               int has_output, int max_ubatch);
+/* What build_qwen2moe (src/llama.cpp:12248-12392) needs beside kcpp_hparams, which stays as it is.  n_ff_shexp > 0:
+ * every layer has a shared expert of that width behind a sigmoid gate, hp.n_ff is the width of one routed expert, and
+ * the per-layer order grows to 14: ... ffn_gate_inp, ffn_gate_inp_shexp [n_embd] (F32 / F16), ffn_gate_shexp
+ * [n_embd, n_ff_shexp], ffn_up_shexp, ffn_down_shexp [n_ff_shexp, n_embd];
+ * x = ((sum_j w_j expert_j(n)) + silu(z) / z * FFN_shexp(n)) + x with n = ffn_norm(x), z = ffn_gate_inp_shexp . n.
+ * moe_norm_w = 0: the routing weights are the selected softmax probabilities as they are (1: divided by their sum).
+ * ex null, or {0, 1}: kcpp_model_create. */
+typedef struct {
+    int n_ff_shexp;
+    int moe_norm_w;
+} kcpp_model_ex;
+kcpp_model *kcpp_model_create_ex(const kcpp_hparams *hp, const kcpp_model_ex *ex, const int *types, int device, int il0,
+                                 int il1, int has_embed, int has_output, int max_ubatch);
 /* weights: synthetic (seed) or uploaded from host ggml-layout bytes (tensor index = canonical order) */
 int kcpp_model_synth_weights(kcpp_model *m, uint64_t seed);
 int kcpp_model_set_tensor(kcpp_model *m, int index, const void *ggml_bytes, int64_t nbytes);
@@ -591,6 +618,11 @@ int64_t kcpp_model_weight_bytes(kcpp_model *m);
  * hand-off ran on RCCL}.  0 ok, -1 fewer than n_dev GPUs visible. */
 int kcpp_engine_bench(const kcpp_hparams *hp, const int *types, int n_types, int n_dev, const float *tensor_split,
                       uint64_t seed, int n_prompt, int ub, int n_warm, int n_steps, double *out);
+/* the same with kcpp_model_create_ex's extension (ex null: kcpp_engine_bench); a model with a shared expert runs NeoX
+ * rope pairs, as load_model sets them for qwen2moe */
+int kcpp_engine_bench_ex(const kcpp_hparams *hp, const kcpp_model_ex *ex, const int *types, int n_types, int n_dev,
+                         const float *tensor_split, uint64_t seed, int n_prompt, int ub, int n_warm, int n_steps,
+                         double *out);
 /* bench / test hook: the model load_model() holds gets the runtime's synthetic weights (kcpp_model_synth_weights per
  * stage; bench.py's generate() leg loads a sparse full-size GGUF, then this); 0 on success, -1 without a model */
 int kcpp_expose_synth_weights(uint64_t seed);

@@ -78,6 +78,7 @@ struct Engine {
     gguf::File file;
     Tokenizer tok;
     kcpp_hparams hp{};
+    kcpp_model_ex ex{0, 1};                 // qwen2moe: the shared expert's width, raw top-k weights
     std::vector<int> types;
     std::vector<kcpp_model *> stages;
     std::vector<float *> hidden;            // per stage residual stream (device)
@@ -440,7 +441,7 @@ bool build_stages(Engine &e, int ndev, int nreal, const float *tensor_split, boo
     // (act - 1) / act, src/llama.cpp:7030-7033) -- a head-only stage when that is not the last layers' device
     auto add_stage = [&](int d, int i0, int i1, bool out) {
         const int gpu = d % nreal;
-        kcpp_model *m = kcpp_model_create(&hp, e.types.data(), gpu, i0, i1, e.stages.empty(), out, e.ub);
+        kcpp_model *m = kcpp_model_create_ex(&hp, &e.ex, e.types.data(), gpu, i0, i1, e.stages.empty(), out, e.ub);
         if (!m) { fprintf(stderr, "[kcpp] load_model: %s\n", kcpp_last_error()); return false; }
         e.stages.push_back(m);
         e.hidden.push_back(kcpp_model_hidden(m));
@@ -459,7 +460,7 @@ bool build_stages(Engine &e, int ndev, int nreal, const float *tensor_split, boo
         const int main_dev = std::min(main_gpu <= 0 ? 0 : main_gpu, nd - 1) % nreal;
         std::vector<int> devs(nd);
         for (int i = 0; i < nd; ++i) devs[i] = i % nreal;
-        kcpp_model *m = kcpp_model_create(&hp, e.types.data(), main_dev, 0, hp.n_layer, 1, 1, e.ub);
+        kcpp_model *m = kcpp_model_create_ex(&hp, &e.ex, e.types.data(), main_dev, 0, hp.n_layer, 1, 1, e.ub);
         if (!m) { fprintf(stderr, "[kcpp] load_model: %s\n", kcpp_last_error()); return false; }
         e.stages.push_back(m);
         e.hidden.push_back(kcpp_model_hidden(m));
@@ -868,7 +869,10 @@ bool load_model(const load_model_inputs inputs) {
     const std::string arch = f.get_s("general.architecture", "");
     // llama, or qwen2 (the Llama graph with q / k / v biases and NeoX rope pairs: build_qwen2, src/llama.cpp:12136-12246);
     // the hyper-parameters live under the architecture's own prefix
-    const bool qwen2 = arch == "qwen2";
+    // qwen2moe (build_qwen2moe, :12248-12392): qwen2's attention, experts with unnormalised top-k weights and a shared
+    // expert behind a sigmoid gate in every layer
+    const bool qmoe = arch == "qwen2moe";
+    const bool qwen2 = arch == "qwen2" || qmoe;
     const std::string pfx = arch + ".";
     if (arch != "llama" && !qwen2) { fprintf(stderr, "[kcpp] load_model: architecture '%s' not supported\n", arch.c_str()); return false; }
     if (!e->tok.init(f, err)) { fprintf(stderr, "[kcpp] load_model: %s\n", err.c_str()); return false; }
@@ -922,17 +926,35 @@ bool load_model(const load_model_inputs inputs) {
                             "ratio of at most 8)\n", hp.n_head, hkv);
             return false;
         }
-        if (f.get_i(pfx + "expert_count", 0) > 0) { fprintf(stderr, "[kcpp] load_model: qwen2 with experts is not supported\n"); return false; }
+        if (!qmoe && f.get_i(pfx + "expert_count", 0) > 0) { fprintf(stderr, "[kcpp] load_model: qwen2 with experts is not supported\n"); return false; }
     }
     // mixture of experts (llm_load_hparams / llm_load_tensors, src/llama.cpp:5444-5445, 7176-7215)
     hp.n_expert = (int)f.get_i(pfx + "expert_count", 0);
     hp.n_expert_used = (int)f.get_i(pfx + "expert_used_count", 0);
-    if (hp.n_expert > 0 && (hp.n_expert_used < 1 || hp.n_expert_used > hp.n_expert || hp.n_expert > 64)) {
-        fprintf(stderr, "[kcpp] load_model: unsupported expert_count %d / expert_used_count %d\n", hp.n_expert,
-                hp.n_expert_used);
+    if ((hp.n_expert > 0 || qmoe) && (hp.n_expert_used < 1 || hp.n_expert_used > hp.n_expert || hp.n_expert > 64)) {
+        if (qmoe)
+            fprintf(stderr, "[kcpp] load_model: architecture 'qwen2moe' not supported with %sexpert_count %d / "
+                            "%sexpert_used_count %d (need 1..64 experts, 1..expert_count of them used)\n",
+                    pfx.c_str(), hp.n_expert, pfx.c_str(), hp.n_expert_used);
+        else
+            fprintf(stderr, "[kcpp] load_model: unsupported expert_count %d / expert_used_count %d\n", hp.n_expert,
+                    hp.n_expert_used);
         return false;
     }
-    const int LW = hp.n_expert > 0 ? 10 : 9;
+    if (qmoe) {
+        // the experts' and the shared expert's widths, with the reference's fallbacks for files that lack the keys
+        // (llm_load_tensors, src/llama.cpp:7814, 7821); hp.n_ff is the width of one expert from here on
+        const int n_ff_all = hp.n_ff;
+        hp.n_ff = (int)f.get_i(pfx + "expert_feed_forward_length", n_ff_all / hp.n_expert_used);
+        e->ex.n_ff_shexp = (int)f.get_i(pfx + "expert_shared_feed_forward_length", n_ff_all);
+        e->ex.moe_norm_w = 0;
+        if (hp.n_ff <= 0 || e->ex.n_ff_shexp <= 0) {
+            fprintf(stderr, "[kcpp] load_model: %sexpert_feed_forward_length %d / %sexpert_shared_feed_forward_length %d\n",
+                    pfx.c_str(), hp.n_ff, pfx.c_str(), e->ex.n_ff_shexp);
+            return false;
+        }
+    }
+    const int LW = hp.n_expert > 0 ? (qmoe ? 14 : 10) : 9;
     // canonical tensor order: tok_embd, output_norm, output, layers x LW (+ ffn_gate_inp for MoE);
     // MoE gate/up/down are the 3-D *_exps tensors, or the older per-expert tensors concatenated
     struct Src { const gguf::Tensor *t = nullptr; int type = 0; int64_t bytes = 0; const uint8_t *data = nullptr; };
@@ -975,7 +997,33 @@ bool load_model(const load_model_inputs inputs) {
                 ts[k].bytes = (int64_t)merged.back().size();
             }
         }
-        if (LW == 10) set(3 + LW * il + 9, f.tensor(b + "ffn_gate_inp.weight"));
+        if (LW >= 10) set(3 + LW * il + 9, f.tensor(b + "ffn_gate_inp.weight"));
+        if (qmoe) {
+            static const char *sh[4] = {"ffn_gate_inp_shexp", "ffn_gate_shexp", "ffn_up_shexp", "ffn_down_shexp"};
+            for (int j = 0; j < 4; ++j) {
+                const std::string name = b + sh[j] + ".weight";
+                const gguf::Tensor *t = f.tensor(name);
+                if (!t) { fprintf(stderr, "[kcpp] load_model: %s: missing tensor\n", name.c_str()); return false; }
+                set(3 + LW * il + 10 + j, t);
+            }
+            const gguf::Tensor *gv = ts[3 + LW * il + 10].t;
+            if ((gv->type != KT_F32 && gv->type != KT_F16) || gv->ne[0] != hp.n_embd || gv->ne[1] * gv->ne[2] * gv->ne[3] != 1) {
+                fprintf(stderr, "[kcpp] load_model: %s: expected %d F32 or F16 values (type %d, length %lld)\n",
+                        gv->name.c_str(), hp.n_embd, gv->type, (long long)gv->ne[0]);
+                return false;
+            }
+            const gguf::Tensor *rt = ts[3 + LW * il + 9].t;
+            if (rt && rt->type != KT_F32 && rt->type != KT_F16) {
+                fprintf(stderr, "[kcpp] load_model: %s: the router must be F32 or F16 (type %d)\n", rt->name.c_str(), rt->type);
+                return false;
+            }
+            for (int j = 6; j <= 8; ++j)
+                if (!ts[3 + LW * il + j].t || ts[3 + LW * il + j].t->ne[2] != hp.n_expert) {
+                    fprintf(stderr, "[kcpp] load_model: %s%s.weight: missing, or not a 3-D tensor of %d experts\n", b.c_str(),
+                            exps[j - 6], hp.n_expert);
+                    return false;
+                }
+        }
     }
     e->types.resize(ts.size());
     for (size_t k = 0; k < ts.size(); ++k) {
@@ -1388,6 +1436,13 @@ int kcpp_pieces_probe(const char *gguf_path, char *out, int64_t cap, int64_t *en
 // out = {prefill_s, decode_s (the n_steps timed tokens), n_past at the end, 1 when the hand-off is RCCL}.
 int kcpp_engine_bench(const kcpp_hparams *hp, const int *types, int n_types, int n_dev, const float *tensor_split,
                       uint64_t seed, int n_prompt, int ub, int n_warm, int n_steps, double *out) {
+    return kcpp_engine_bench_ex(hp, nullptr, types, n_types, n_dev, tensor_split, seed, n_prompt, ub, n_warm, n_steps, out);
+}
+
+// the same for a model with kcpp_model_create_ex's extension (qwen2moe shapes: 14 tensors per layer, NeoX pairs)
+int kcpp_engine_bench_ex(const kcpp_hparams *hp, const kcpp_model_ex *ex, const int *types, int n_types, int n_dev,
+                         const float *tensor_split, uint64_t seed, int n_prompt, int ub, int n_warm, int n_steps,
+                         double *out) {
     if (!hp || !types || !out || n_dev < 1 || n_prompt < 1 || n_prompt + n_warm + n_steps + 1 > hp->n_ctx) return -2;
     int nreal = 0;                          // KCPP_VIRTUAL_DEVICES (tests): several stages per GPU, stage i on GPU i % nreal
     if (hipGetDeviceCount(&nreal) != hipSuccess || nreal < 1 || (nreal < n_dev && !getenv("KCPP_VIRTUAL_DEVICES"))) {
@@ -1397,13 +1452,14 @@ int kcpp_engine_bench(const kcpp_hparams *hp, const int *types, int n_types, int
     nreal = std::min(nreal, n_dev);
     auto e = std::make_unique<Engine>();
     e->hp = *hp;
+    if (ex) e->ex = *ex;
     e->types.assign(types, types + n_types);
     e->ub = std::max(1, std::min(ub, 512));
     float ts[KCPP_TENSOR_SPLIT_MAX] = {0};
     for (int i = 0; i < n_dev && i < KCPP_TENSOR_SPLIT_MAX; ++i) ts[i] = tensor_split ? tensor_split[i] : 1.0f;
     if (!build_stages(*e, n_dev, nreal, ts, false, 0) || !init_handoff(*e)) return -3;
     for (kcpp_model *m : e->stages)
-        if (kcpp_model_synth_weights(m, seed)) return -4;
+        if (kcpp_model_synth_weights(m, seed) || (ex && ex->n_ff_shexp > 0 && kcpp_model_set_rope_mode(m, 2))) return -4;
     std::vector<int32_t> prompt(n_prompt);
     for (int i = 0; i < n_prompt; ++i) prompt[i] = 16 + (i % 2);          // the " 1" pattern of bench.py
     kcpp_model *last = e->stages.back();

@@ -109,7 +109,9 @@ struct AuxOut {
 
 // top-NU of NE <= 8 router logits exactly as ggml's soft_max (ggml_float sum) + argsort (exchange order) + the
 // normalisation by the selected weights' sum (llm_build_moe_ffn, src/llama.cpp:9416-9470); shared by k_moe_route
-// (moe.hip) and the routed RS GLU launch (gemv_rs.hip) so both choose bit-identical experts and weights
+// (moe.hip) and the routed RS GLU launch (gemv_rs.hip) so both choose bit-identical experts and weights.
+// RAW: the selected probabilities as they are (llm_build_moe_ffn with norm_w = false, build_qwen2moe)
+template <bool RAW = false>
 __device__ __forceinline__ void moe_topk8(const float *logit, int NE, int NU, int *idx_out, float *w_out) {
     float p[8], pv[8];
     int idx[8];
@@ -137,6 +139,12 @@ __device__ __forceinline__ void moe_topk8(const float *logit, int NE, int NU, in
                 const float tv = pv[j]; pv[j] = pv[k]; pv[k] = tv;
             }
         }
+    }
+    if constexpr (RAW) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (j < NU) { idx_out[j] = idx[j]; w_out[j] = pv[j]; }
+        return;
     }
     double ws = 0.0;
 #pragma unroll

@@ -90,7 +90,8 @@ struct Lane {
 };
 
 struct KLayer {
-    KTensor t[10];  // attn_norm, wq, wk, wv, wo, ffn_norm, gate, up, down (, ffn_gate_inp for MoE)
+    KTensor t[14];  // attn_norm, wq, wk, wv, wo, ffn_norm, gate, up, down (, ffn_gate_inp for MoE (, ffn_gate_inp_shexp,
+                    // ffn_gate_shexp, ffn_up_shexp, ffn_down_shexp with a shared expert))
     uint16_t *kc = nullptr, *vc = nullptr;
     // prefill fusion: same-type row-major (Q4_K/Q5_K) weights sharing one input are stored back to back,
     // so q|k(|v) and gate|up each run as ONE GEMM over the concatenated rows (one activation conversion,
@@ -105,8 +106,14 @@ struct CandCtx;                          // the sampling front end's buffers (be
 static CandCtx *cand_create(int n, int cap, int64_t max_ops);
 static void cand_free(CandCtx *c);
 
+// kcpp_hparams plus what kcpp_model_create_ex carries beside it (kcpp_model_ex)
+struct HP : kcpp_hparams {
+    int n_ff_shexp = 0;              // width of the shared expert (build_qwen2moe); 0: none
+    int moe_norm_w = 1;              // 1: top-k weights divided by their sum (llm_build_moe_ffn norm_w)
+};
+
 struct kcpp_model {
-    kcpp_hparams hp;
+    HP hp;
     std::vector<int> types;
     int device = 0, il0 = 0, il1 = 0, has_embed = 1, has_output = 1, ub = 512;
     hipStream_t stream = nullptr;
@@ -126,6 +133,8 @@ struct kcpp_model {
     int32_t *moe_rows = nullptr;     // prefill, grouped by expert: [ubatch*k] token rows ++ [ubatch*k] slot rows
     float *moe_rw = nullptr;         // [ubatch*k] routing weight of each grouped entry
     float *moe_slots = nullptr;      // [k][ubatch][n_embd] weighted expert outputs, summed in top-k order
+    float *moe_gate = nullptr;       // [ubatch] the shared expert's gate silu(z) / z (device)
+    float *moe_sh = nullptr;         // [ubatch][n_embd] the shared expert's output where no epilogue carries it
     int32_t *moe_trace = nullptr;    // [n_layer of the stage][n_expert_used] single-token routing (diagnostics)
     bool no_fused_route = false;     // MoE decode: route in k_moe_route instead of inside the gate|up launch (A/B tests)
     int64_t n_fused_route = 0;       // routed gate|up launches enqueued (tests: the fused path really ran)
@@ -191,16 +200,17 @@ static int64_t tensor_bytes(int type, int64_t K, int64_t N) {
     return K / ks_block_elems(type) * N * ks_block_bytes(type);
 }
 
-static int per_layer(const kcpp_hparams &hp) { return hp.n_expert > 0 ? 10 : 9; }
-static int n_tensors(const kcpp_hparams &hp) { return 3 + per_layer(hp) * hp.n_layer; }
-static int n_slices(const kcpp_hparams &hp, int idx) {
+static int per_layer(const HP &hp) { return hp.n_expert > 0 ? (hp.n_ff_shexp > 0 ? 14 : 10) : 9; }
+static int n_tensors(const HP &hp) { return 3 + per_layer(hp) * hp.n_layer; }
+static int n_slices(const HP &hp, int idx) {
     if (idx < 3 || hp.n_expert <= 0) return 1;
-    const int j = (idx - 3) % 10;
+    const int j = (idx - 3) % per_layer(hp);
     return (j >= 6 && j <= 8) ? hp.n_expert : 1;
 }
 
-static void shape_of(const kcpp_hparams &hp, int idx, int64_t &K, int64_t &N) {
+static void shape_of(const HP &hp, int idx, int64_t &K, int64_t &N) {
     const int64_t E = hp.n_embd, F = hp.n_ff, V = hp.n_vocab, EKV = (int64_t)hp.n_head_kv * (E / hp.n_head);
+    const int64_t FS = hp.n_ff_shexp;
     if (idx == 0) { K = E; N = V; return; }
     if (idx == 1) { K = E; N = 1; return; }
     if (idx == 2) { K = E; N = V; return; }
@@ -214,7 +224,11 @@ static void shape_of(const kcpp_hparams &hp, int idx, int64_t &K, int64_t &N) {
     case 6: K = E; N = F; return;
     case 7: K = E; N = F; return;
     case 8: K = F; N = E; return;
-    default: K = E; N = hp.n_expert; return;    // ffn_gate_inp (router)
+    case 9: K = E; N = hp.n_expert; return;     // ffn_gate_inp (router)
+    case 10: K = E; N = 1; return;              // ffn_gate_inp_shexp
+    case 11: K = E; N = FS; return;
+    case 12: K = E; N = FS; return;
+    default: K = FS; N = E; return;             // ffn_down_shexp
     }
 }
 
@@ -360,11 +374,21 @@ extern "C" int kcpp_model_set_qkv_bias(kcpp_model *m, int il, const float *bq, c
 
 extern "C" kcpp_model *kcpp_model_create(const kcpp_hparams *hp, const int *types, int device, int il0, int il1,
                                          int has_embed, int has_output, int max_ubatch) {
+    return kcpp_model_create_ex(hp, nullptr, types, device, il0, il1, has_embed, has_output, max_ubatch);
+}
+
+extern "C" kcpp_model *kcpp_model_create_ex(const kcpp_hparams *hp0, const kcpp_model_ex *ex, const int *types, int device,
+                                            int il0, int il1, int has_embed, int has_output, int max_ubatch) {
+    HP hpx;
+    (kcpp_hparams &)hpx = *hp0;
+    if (ex) { hpx.n_ff_shexp = ex->n_ff_shexp; hpx.moe_norm_w = ex->moe_norm_w != 0; }
+    if (hpx.n_ff_shexp < 0 || (hpx.n_ff_shexp > 0 && hpx.n_expert <= 0)) { g_err = "a shared expert needs n_expert > 0"; return nullptr; }
+    const HP *hp = &hpx;
     if (hipSetDevice(device) != hipSuccess) { g_err = "hipSetDevice failed"; return nullptr; }
     // the split-KV decode attention merges at most 2048 chunks of 64 keys (fa_plan.h FA_MAX_CHUNKS)
     if (hp->n_ctx < 1 || hp->n_ctx > 131072) { g_err = "n_ctx must be in [1, 131072]"; return nullptr; }
     kcpp_model *m = new kcpp_model();
-    m->hp = *hp;
+    m->hp = hpx;
     // on-device layout per tensor: dense Q4_K / Q5_K / Q6_K mat-mul weights whose K the RS kernels cover are held in
     // the row-major decode layouts (KT_Q4_K_RS / KT_Q5_K_RS / KT_Q6_K_RS, gemv_rs.hip), expert slices too (each slice
     // its own RS tensor: the RS kernels take the device-resident expert index, the GEMMs read RS planes); the token
@@ -374,7 +398,7 @@ extern "C" kcpp_model *kcpp_model_create(const kcpp_hparams *hp, const int *type
         int t = types[idx];
         int64_t K, N;
         shape_of(*hp, idx, K, N);
-        const bool dense = idx >= 2 && N > 1 && (idx == 2 || (idx - 3) % per_layer(*hp) <= 8);
+        const bool dense = idx >= 2 && N > 1 && (idx == 2 || (idx - 3) % per_layer(*hp) != 9);   // not the router
         if (dense && (t == KT_Q4_K || t == KT_Q5_K || t == KT_Q6_K) && kcpp_rs_supported(t, K))
             t = t == KT_Q4_K ? KT_Q4_K_RS : (t == KT_Q5_K ? KT_Q5_K_RS : KT_Q6_K_RS);
         m->types[idx] = t;
@@ -412,7 +436,8 @@ extern "C" kcpp_model *kcpp_model_create(const kcpp_hparams *hp, const int *type
         hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&m->ev_join, hipEventDisableTiming) != hipSuccess)
         return fail("side stream");
-    const int64_t E = hp->n_embd, F = hp->n_ff, H = hp->n_head, HKV = hp->n_head_kv, D = E / H, EKV = HKV * D;
+    // F: the widest FFN row any scratch buffer holds (an expert's, or the shared expert's)
+    const int64_t E = hp->n_embd, F = std::max(hp->n_ff, hp->n_ff_shexp), H = hp->n_head, HKV = hp->n_head_kv, D = E / H, EKV = HKV * D;
     const int64_t UB = m->ub;
     m->layers.resize(il1 - il0);
     auto rowmajor = [](int t) { return t == KT_Q4_K || t == KT_Q5_K || t == KT_Q4_K_RS || t == KT_Q5_K_RS || t == KT_Q6_K_RS; };
@@ -529,8 +554,8 @@ extern "C" kcpp_model *kcpp_model_create(const kcpp_hparams *hp, const int *type
             static const int qkv[3] = {1, 2, 3}, glu[2] = {6, 7};
             if (L.nqkv >= 2) img_group(L.t, qkv, L.nqkv);
             if (L.glu_fused) img_group(L.t, glu, 2);
-            for (int j = 1; j <= 8 && ok3; ++j) {
-                if (j == 5 || L.t[j].pre) continue;
+            for (int j = 1; j < per_layer(*hp) && ok3; ++j) {
+                if (j == 5 || j == 9 || j == 10 || L.t[j].pre) continue;
                 const int one[1] = {j};
                 img_group(L.t, one, 1);
             }
@@ -550,6 +575,7 @@ extern "C" kcpp_model *kcpp_model_create(const kcpp_hparams *hp, const int *type
         if (hipMalloc(&m->moe_ids, UB * NU * 4) != hipSuccess || hipMalloc(&m->moe_w, UB * NU * 4) != hipSuccess ||
             hipMalloc(&m->moe_rows, 2 * UB * NU * 4) != hipSuccess || hipMalloc(&m->moe_rw, UB * NU * 4) != hipSuccess ||
             hipMalloc(&m->moe_slots, NU * UB * E * 4) != hipSuccess ||
+            (hp->n_ff_shexp > 0 && (hipMalloc(&m->moe_gate, UB * 4) != hipSuccess || hipMalloc(&m->moe_sh, UB * E * 4) != hipSuccess)) ||
             hipHostMalloc((void **)&m->moe_ids_h, UB * NU * 4, hipHostMallocDefault) != hipSuccess ||
             hipHostMalloc((void **)&m->moe_w_h, UB * NU * 4, hipHostMallocDefault) != hipSuccess ||
             hipHostMalloc((void **)&m->moe_rows_h, 2 * UB * NU * 4, hipHostMallocDefault) != hipSuccess ||
@@ -594,7 +620,7 @@ extern "C" void kcpp_model_free(kcpp_model *m) {
         for (auto &t : L.t) { if (t.owned) F(t.d); FS(t); F(t.dec); if (t.pre_owned) F(t.pre); }
         F(L.qkv_base); F(L.glu_base); F(L.kc); F(L.vc); F(L.bq);
     }
-    F(m->hglu); F(m->moe_ids); F(m->moe_w); F(m->moe_rows); F(m->moe_rw); F(m->moe_slots);
+    F(m->hglu); F(m->moe_ids); F(m->moe_w); F(m->moe_rows); F(m->moe_rw); F(m->moe_slots); F(m->moe_gate); F(m->moe_sh);
     F(m->moe_gx); F(m->moe_gh); F(m->moe_gup); F(m->moe_geo); F(m->moe_gact); F(m->moe_gcnt); F(m->moe_gws);
     for (void *p : {(void *)m->moe_ids_h, (void *)m->moe_w_h, (void *)m->moe_rows_h, (void *)m->moe_rw_h,
                     (void *)m->moe_gcnt_h})
@@ -1199,12 +1225,115 @@ static int matmul(kcpp_model *m, const KTensor &W, const KTensor *W2, const void
 // ffn_norm -> router/softmax/top-k on the GPU (moe_ids, moe_w), then per top-k slot j the expert's
 // gate|up and down mat-vecs read their expert index from moe_ids[j] (DecArgs.eid) and down writes
 // w_j * out into slot j; the combine sums the slots in top-k order and adds the residual.
+// the router of a layer whose weights stay unnormalised or that has a shared expert (build_qwen2moe): m->attn holds the
+// T normalised rows; the shared expert's gate goes to m->moe_gate in the same launch
+static int moe_route_ex(kcpp_model *m, const KLayer &L, int T) {
+    const HP &hp = m->hp;
+    const KTensor *t = L.t;
+    const bool sh = hp.n_ff_shexp > 0;
+    return kcpp_moe_route_ex(m->attn, hp.n_embd, t[9].d, t[9].type, hp.n_embd, hp.n_expert, hp.n_expert_used, hp.moe_norm_w,
+                             sh ? t[10].d : nullptr, sh ? t[10].type : 0, m->moe_ids, m->moe_w, m->moe_gate, T, m->stream);
+}
+
+// the shared expert over the T normalised rows in m->attn, on the dense FFN's unfused plan (one GLU GEMM, one down
+// GEMM): FFN_shexp(n) -> m->moe_sh [T][n_embd]
+static int moe_shexp_rows(kcpp_model *m, const KLayer &L, int T) {
+    const HP &hp = m->hp;
+    const int64_t E = hp.n_embd, FS = hp.n_ff_shexp;
+    const KTensor *t = L.t;
+    hipStream_t s = m->stream;
+    const int vg = kcpp_vec_dot_type(t[11].type), vu = kcpp_vec_dot_type(t[12].type);
+    RC(kcpp_quantize_act(vg, m->attn, E, m->act, E, T, s));
+    if (t[11].type == t[12].type) {
+        RC(matmul(m, t[11], &t[12], m->act, T, m->h, FS, nullptr, 0, 1));             // h = silu(g) * u
+    } else {
+        RC(matmul(m, t[11], nullptr, m->act, T, m->h, FS, nullptr, 0, 0));
+        if (vu != vg) RC(kcpp_quantize_act(vu, m->attn, E, m->act, E, T, s));
+        RC(matmul(m, t[12], nullptr, m->act, T, m->hglu, FS, nullptr, 0, 0));
+        RC(kcpp_silu_mul(m->h, m->h, m->hglu, (int64_t)T * FS, s));
+    }
+    RC(kcpp_quantize_act(kcpp_vec_dot_type(t[13].type), m->h, FS, m->act2, FS, T, s));
+    return matmul(m, t[13], nullptr, m->act2, T, m->moe_sh, E, nullptr, 0, 0);
+}
+
+// the end of a MoE FFN whose weighted expert outputs sit in m->moe_slots [k][T][n_embd]: their sum in top-k order, the
+// gated shared expert where the model has one, the residual (k_moe_combine / k_moe_combine_shexp)
+static int moe_finish(kcpp_model *m, const KLayer &L, int T) {
+    const HP &hp = m->hp;
+    const int64_t n = (int64_t)T * hp.n_embd;
+    if (hp.n_ff_shexp <= 0) return kcpp_moe_combine(m->x, m->moe_slots, n, hp.n_expert_used, n, m->stream);
+    RC(moe_shexp_rows(m, L, T));
+    return kcpp_moe_combine_shexp(m->x, m->moe_slots, n, hp.n_expert_used, m->moe_gate, m->moe_sh, hp.n_embd, T, m->stream);
+}
+
+// single-token shared expert on the fused mat-vecs, as the dense FFN runs them (the ffn_norm prologue recomputed); the
+// routed sum sits in m->moe_slots [n_embd] (nslots 0: carried through the down projections) or in nslots slots.  Its
+// down projection's epilogue is (pre + escale * product) + res = (routed + gate * sh) + x in the row-major K-quant
+// layouts alone: only their store (gemv_lean.h store_group) reads DecArgs.pre, and the plan has no flag for it, so
+// another family would run and drop the routed sum.  Every other type, and a kernel that refuses (-3 / -8), stores
+// the product and k_moe_combine_shexp does the same arithmetic
+static int moe_shexp_dec(kcpp_model *m, const KLayer &L, int nslots) {
+    const HP &hp = m->hp;
+    const int64_t E = hp.n_embd, FS = hp.n_ff_shexp;
+    const KTensor *t = L.t;
+    hipStream_t s = m->stream;
+    auto norm_arg = [&](DecArgs &a) {
+        memset(&a, 0, sizeof a);
+        a.K = E; a.x = m->x; a.nw = (const float *)t[5].d; a.eps = hp.eps; a.nseg = 1;
+    };
+    int rc;
+    if (t[11].type == t[12].type) {
+        DecArgs a;
+        norm_arg(a);
+        a.W[0] = (const uint8_t *)t[11].d; a.W2 = (const uint8_t *)t[12].d; a.N[0] = FS; a.Y[0] = m->h;
+        rc = kcpp_gemv_dec(t[11].type, &a, 1, 1, gemv_rows_per_wave(FS, 1), s);
+    } else {
+        rc = 0;
+        for (int j = 11; j <= 12 && rc == 0; ++j) {
+            DecArgs a;
+            norm_arg(a);
+            a.W[0] = (const uint8_t *)t[j].d; a.N[0] = FS; a.Y[0] = j == 11 ? m->h : m->hglu;   // hglu: 2 max(n_ff) floats a row
+            rc = kcpp_gemv_dec(t[j].type, &a, 0, 1, gemv_rows_per_wave(FS, 0), s);
+        }
+        if (rc == 0) RC(kcpp_silu_mul(m->h, m->h, m->hglu, FS, s));
+    }
+    if (rc == -3 || rc == -8) {          // no fused mat-vec for this type or width: the GEMM plan on the normalised row
+        RC(kcpp_rms_norm(m->x, E, (const float *)t[5].d, m->attn, E, nullptr, E, 1, hp.eps, s));
+        RC(moe_shexp_rows(m, L, 1));
+        return kcpp_moe_combine_shexp(m->x, m->moe_slots, E, std::max(1, nslots), m->moe_gate, m->moe_sh, E, 1, s);
+    }
+    RC(rc);
+    DecArgs a;
+    memset(&a, 0, sizeof a);
+    a.K = FS; a.x = m->h; a.nseg = 1;
+    a.W[0] = (const uint8_t *)t[13].d; a.N[0] = E;
+    const bool carries_pre = t[13].type == KT_Q4_K_RS || t[13].type == KT_Q5_K_RS || t[13].type == KT_Q6_K_RS;
+    if (nslots == 0 && carries_pre) {
+        a.Y[0] = m->x; a.res = m->x; a.pre = m->moe_slots; a.escale = m->moe_gate;
+        rc = kcpp_gemv_dec(t[13].type, &a, 0, 2, gemv_rows_per_wave(E, 0), s);
+        if (rc == 0) return 0;
+        if (rc != -3 && rc != -8) return rc;
+        a.res = nullptr; a.pre = nullptr; a.escale = nullptr;
+    }
+    a.Y[0] = m->moe_sh;
+    rc = kcpp_gemv_dec(t[13].type, &a, 0, 2, gemv_rows_per_wave(E, 0), s);
+    if (rc == -3 || rc == -8) {
+        RC(kcpp_quantize_act(kcpp_vec_dot_type(t[13].type), m->h, FS, m->act2, FS, 1, s));
+        RC(kcpp_gemv(t[13].type, t[13].d, nullptr, FS, E, m->act2, 1, m->moe_sh, E, nullptr, 0, 0, s));
+    } else {
+        RC(rc);
+    }
+    return kcpp_moe_combine_shexp(m->x, m->moe_slots, E, std::max(1, nslots), m->moe_gate, m->moe_sh, E, 1, s);
+}
+
 static int moe_dec(kcpp_model *m, const KLayer &L) {
-    const kcpp_hparams &hp = m->hp;
+    const HP &hp = m->hp;
     const int64_t E = hp.n_embd, F = hp.n_ff;
     const int NU = hp.n_expert_used;
     const KTensor *t = L.t;
     hipStream_t s = m->stream;
+    // build_qwen2moe's layers: unnormalised weights and / or a shared expert; never the in-launch router
+    const bool shexp = hp.n_ff_shexp > 0, ext = shexp || !hp.moe_norm_w;
     auto is_q81 = [](int ty) { return ty == KT_Q4_1 || ty == KT_Q5_1; };
     // RS gate|up with two slots: both slots' GLU rows in one launch (segment j = slot j, its own expert index), one
     // ramp instead of two; h of slot j at m->h + j F.  The router runs inside that launch where it can (top-2 of <= 8
@@ -1213,7 +1342,7 @@ static int moe_dec(kcpp_model *m, const KLayer &L) {
                        (t[6].type == KT_Q4_K_RS || t[6].type == KT_Q5_K_RS || t[6].type == KT_Q6_K_RS);
     const bool pair = rs_gu && NU == 2 && m->ub >= 2;
     bool routed = false;
-    if (pair && !m->no_fused_route && (t[9].type == KT_F32 || t[9].type == KT_F16) && hp.n_expert <= 8 && E <= 4096) {
+    if (pair && !ext && !m->no_fused_route && (t[9].type == KT_F32 || t[9].type == KT_F16) && hp.n_expert <= 8 && E <= 4096) {
         DecArgs a;
         memset(&a, 0, sizeof a);
         a.K = E; a.x = m->x; a.nw = (const float *)t[5].d; a.eps = hp.eps; a.nseg = 2;
@@ -1227,7 +1356,14 @@ static int moe_dec(kcpp_model *m, const KLayer &L) {
         routed = rc == 0;
         m->n_fused_route += routed;
     }
-    if (!routed &&
+    if (ext) {
+        if (kcpp_moe_route_norm_ex(m->x, E, (const float *)t[5].d, hp.eps, t[9].d, t[9].type, E, hp.n_expert, NU,
+                                   hp.moe_norm_w, shexp ? t[10].d : nullptr, shexp ? t[10].type : 0, m->moe_ids, m->moe_w,
+                                   m->moe_gate, 1, s) != 0) {
+            RC(kcpp_rms_norm(m->x, E, (const float *)t[5].d, m->attn, E, nullptr, E, 1, hp.eps, s));
+            RC(moe_route_ex(m, L, 1));
+        }
+    } else if (!routed &&
         kcpp_moe_route_norm(m->x, E, (const float *)t[5].d, hp.eps, t[9].d, t[9].type, E, hp.n_expert, NU, m->moe_ids,
                             m->moe_w, 1, s) != 0) {
         RC(kcpp_rms_norm(m->x, E, (const float *)t[5].d, m->attn, E, nullptr, E, 1, hp.eps, s));
@@ -1260,7 +1396,7 @@ static int moe_dec(kcpp_model *m, const KLayer &L) {
             RC(kcpp_gemv_expert(t[8].type, t[8].d, nullptr, F, E, m->act2, m->moe_slots + j * E, id,
                                 (int64_t)t[8].slice_bytes, hp.n_expert, m->moe_w + j, 0, s));
         }
-        return kcpp_moe_combine(m->x, m->moe_slots, E, NU, E, s);
+        return moe_finish(m, L, 1);          // m->attn still holds the normalised row
     }
     // RS down projections (MODE 0 store epilogue with DecArgs.pre): k_moe_combine's ((s0 + s1) + ...) + x in the
     // same order, one launch per layer less
@@ -1281,10 +1417,11 @@ static int moe_dec(kcpp_model *m, const KLayer &L) {
         memset(&a, 0, sizeof a);
         a.K = F; a.x = m->h; a.nseg = 1;
         a.W[0] = a.W[1] = (const uint8_t *)t[8].d; a.N[0] = E; a.Y[0] = m->x; a.res = m->x;
+        if (shexp) { a.Y[0] = m->moe_slots; a.res = nullptr; }     // the residual is the shared expert's to add
         a.eid = m->moe_ids; a.eid1 = m->moe_ids + 1; a.n_exp = hp.n_expert; a.ebytes = (int64_t)t[8].slice_bytes;
         a.escale = m->moe_w;
         const int rc = kcpp_gemv_dec(t[8].type, &a, 3, 2, gemv_rows_per_wave(E, 0), s);
-        if (rc == 0) { m->n_pair_down++; return 0; }
+        if (rc == 0) { m->n_pair_down++; return shexp ? moe_shexp_dec(m, L, 0) : 0; }
         if (rc != -3) return rc;
     }
     for (int j = 0; j < NU; ++j) {
@@ -1313,9 +1450,10 @@ static int moe_dec(kcpp_model *m, const KLayer &L) {
         a.W[0] = (const uint8_t *)t[8].d; a.N[0] = E; a.Y[0] = m->moe_slots + j * E;
         a.eid = m->moe_ids + j; a.n_exp = hp.n_expert; a.ebytes = (int64_t)t[8].slice_bytes; a.escale = m->moe_w + j;
         if (chain) {            // slot sum carried through the down projections, the last one adds the residual
-            a.Y[0] = j == NU - 1 ? m->x : m->moe_slots;
+            const bool last = j == NU - 1 && !shexp;                 // with a shared expert the sum stays in moe_slots
+            a.Y[0] = last ? m->x : m->moe_slots;
             a.pre = j > 0 ? m->moe_slots : nullptr;
-            a.res = j == NU - 1 ? m->x : nullptr;
+            a.res = last ? m->x : nullptr;
         }
         const int rc = kcpp_gemv_dec(t[8].type, &a, 0, 2, gemv_rows_per_wave(E, 0), s);
         if (rc == -8) {
@@ -1328,6 +1466,7 @@ static int moe_dec(kcpp_model *m, const KLayer &L) {
         }
         RC(rc);
     }
+    if (shexp) return moe_shexp_dec(m, L, chain ? 0 : NU);
     return chain ? 0 : kcpp_moe_combine(m->x, m->moe_slots, E, NU, E, s);
 }
 
@@ -1393,17 +1532,18 @@ static int moe_prefill_grouped(kcpp_model *m, const KLayer &L, int T, const int 
     }
     RC(kcpp_moe_scatter(m->moe_slots, E, m->moe_geo, m->moe_rows + UB * NU, m->moe_rw, (int)R, E, s));
     m->n_moe_grouped++;
-    return kcpp_moe_combine(m->x, m->moe_slots, (int64_t)T * E, NU, (int64_t)T * E, s);
+    return moe_finish(m, L, T);
 }
 
 static int moe_prefill(kcpp_model *m, const KLayer &L, int T) {
-    const kcpp_hparams &hp = m->hp;
+    const HP &hp = m->hp;
     const int64_t E = hp.n_embd, F = hp.n_ff, UB = m->ub;
     const int NU = hp.n_expert_used, NE = hp.n_expert;
     const KTensor *t = L.t;
     hipStream_t s = m->stream;
     RC(kcpp_rms_norm(m->x, E, (const float *)t[5].d, m->attn, E, nullptr, E, T, hp.eps, s));
-    RC(kcpp_moe_route(m->attn, E, t[9].d, t[9].type, E, NE, NU, m->moe_ids, m->moe_w, T, s));
+    if (hp.n_ff_shexp > 0 || !hp.moe_norm_w) RC(moe_route_ex(m, L, T));
+    else RC(kcpp_moe_route(m->attn, E, t[9].d, t[9].type, E, NE, NU, m->moe_ids, m->moe_w, T, s));
     RT_CHECK(hipMemcpyAsync(m->moe_ids_h, m->moe_ids, (size_t)T * NU * 4, hipMemcpyDeviceToHost, s));
     RT_CHECK(hipMemcpyAsync(m->moe_w_h, m->moe_w, (size_t)T * NU * 4, hipMemcpyDeviceToHost, s));
     RT_CHECK(hipStreamSynchronize(s));
@@ -1451,11 +1591,17 @@ static int moe_prefill(kcpp_model *m, const KLayer &L, int T) {
             RC(matmul(m, u, nullptr, m->act, n, eo, F, nullptr, 0, 0));
             RC(kcpp_silu_mul(m->h, m->h, eo, (int64_t)n * F, s));
         }
-        RC(kcpp_quantize_act(kcpp_vec_dot_type(d.type), m->h, F, m->act2, F, n, s));
-        RC(matmul(m, d, nullptr, m->act2, n, eo, E, nullptr, 0, 0));
+        // the GEMMs take K in whole 256-element blocks: an expert width that is not (1408 in Qwen1.5-MoE-A2.7B, whose
+        // ffn_down_exps are Q5_0 / Q8_0 for that reason) goes through the mat-vec kernels, 8 rows a launch
+        const int step = F % 256 ? 8 : n;
+        for (int r0 = 0; r0 < n; r0 += step) {
+            const int nr = std::min(step, n - r0);
+            RC(kcpp_quantize_act(kcpp_vec_dot_type(d.type), m->h + (int64_t)r0 * F, F, m->act2, F, nr, s));
+            RC(matmul(m, d, nullptr, m->act2, nr, eo + (int64_t)r0 * E, E, nullptr, 0, 0));
+        }
         RC(kcpp_moe_scatter(m->moe_slots, E, eo, m->moe_rows + UB * NU + off[e], m->moe_rw + off[e], n, E, s));
     }
-    return kcpp_moe_combine(m->x, m->moe_slots, (int64_t)T * E, NU, (int64_t)T * E, s);
+    return moe_finish(m, L, T);
 }
 
 // a layer's single-token q|k|v without the fused epilogue: attn_norm, the three mat-vecs into m->qkv, then the bias add,

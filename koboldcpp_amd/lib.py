@@ -82,6 +82,7 @@ _SIGS = {
     "kcpp_pieces_probe": [ctypes.c_char_p, P, I64, P, I],
     "kcpp_tokenizer_special_ids": [ctypes.c_char_p, P],
     "kcpp_engine_bench": [P, P, I, I, P, U64, I, I, I, I, P],
+    "kcpp_engine_bench_ex": [P, P, P, I, I, P, U64, I, I, I, I, P],
     "kcpp_expose_synth_weights": [U64],
     "kcpp_gemm_q80t": [P, P, I, P, I64, P, I64, P, I64, P, I64, I, P, P, P],
     "kcpp_gemm_q80t_qkv_rope": [P, P, I64, P, I64, P, I, P, I, P, P, P, P, P],
@@ -94,6 +95,9 @@ _SIGS = {
     "kcpp_add": [P, P, P, I64, P],
     "kcpp_silu_mul": [P, P, P, I64, P],
     "kcpp_moe_route": [P, I64, P, I, I64, I, I, P, P, I, P],
+    "kcpp_moe_route_ex": [P, I64, P, I, I64, I, I, I, P, I, P, P, P, I, P],
+    "kcpp_moe_route_norm_ex": [P, I64, P, Fl, P, I, I64, I, I, I, P, I, P, P, P, I, P],
+    "kcpp_moe_combine_shexp": [P, P, I64, I, P, P, I64, I, P],
     "kcpp_moe_gather": [P, I64, P, I, I64, P, P],
     "kcpp_moe_scatter": [P, I64, P, P, P, I, I64, P],
     "kcpp_moe_combine": [P, P, I64, I, I64, P],
@@ -114,6 +118,7 @@ _SIGS = {
     "kcpp_flash_attn_ext_dec_sc": [P, I64, P, P, I64, I64, P, P, P, I, I, I, I, Fl, P, Fl],
     "kcpp_ggml_gelu_table_init": [],
     "kcpp_model_create": [P, P, I, I, I, I, I, I],
+    "kcpp_model_create_ex": [P, P, P, I, I, I, I, I, I],
     "kcpp_model_synth_weights": [P, U64],
     "kcpp_model_set_tensor": [P, I, P, I64],
     "kcpp_model_free": [P],
@@ -180,7 +185,7 @@ _SIGS = {
     "kcpp_grammar_partial": [P, P],
 }
 _RES = {"kcpp_gradient_ai_rope_base": Fl, "kcpp_q6p_image_bytes": I64, "kcpp_model_fused_route_count": I64, "kcpp_model_moe_grouped_count": I64, "kcpp_gemm_grouped_ws_bytes": I64, "kcpp_fa_split_ws_bytes": I64, "kcpp_q80t_ws_bytes": I64, "kcpp_act_bytes": I64, "kcpp_fa_ext_workspace_bytes": I64, "kcpp_fa_workspace_bytes": I64, "kcpp_gemm_workspace_bytes": I64,
-        "kcpp_model_create": P, "kcpp_model_hidden": P, "kcpp_model_stream": P, "kcpp_model_weight_bytes": I64,
+        "kcpp_model_create": P, "kcpp_model_create_ex": P, "kcpp_model_hidden": P, "kcpp_model_stream": P, "kcpp_model_weight_bytes": I64,
         "kcpp_last_error": ctypes.c_char_p, "kcpp_model_free": None, "kcpp_fa_set_stamps": None,
         "kcpp_expose_set_sample_front": None, "kcpp_expose_sample_front_stats": None, "kcpp_expose_mirostat_mu": Fl,
         "kcpp_expose_grammar_stats": None, "kcpp_expose_grammar_mask_ms": ctypes.c_double, "kcpp_grammar_create": P,
@@ -293,6 +298,11 @@ def hparams(hp):
                    int(hp.get("n_expert", 0)), int(hp.get("n_expert_used", 0)))
 
 
+class ModelEx(ctypes.Structure):
+    """kcpp_model_ex: what build_qwen2moe needs beside kcpp_hparams"""
+    _fields_ = [("n_ff_shexp", ctypes.c_int), ("moe_norm_w", ctypes.c_int)]
+
+
 def engine_bench(hp, types, n_dev, n_prompt, ubatch, n_warm, n_steps, seed=1234, tensor_split=None):
     """the drop-in engine (load_model's layer-split stages over n_dev GPUs, RCCL / copy hand-off, greedy tokens moved
     home on device) on synthetic weights: {prefill_s, decode_s, n_past, rccl}"""
@@ -300,8 +310,13 @@ def engine_bench(hp, types, n_dev, n_prompt, ubatch, n_warm, n_steps, seed=1234,
     t = (ctypes.c_int * len(types))(*types)
     ts = (ctypes.c_float * 16)(*((tensor_split or [1.0] * n_dev) + [0.0] * (16 - n_dev)))
     out = (ctypes.c_double * 4)()
-    _chk(_L.kcpp_engine_bench(ctypes.byref(h), t, len(types), n_dev, ts, seed, n_prompt, ubatch, n_warm, n_steps, out),
-         "engine_bench")
+    if "n_ff_shexp" in hp or "moe_norm_w" in hp:          # qwen2moe shapes: kcpp_model_create_ex's extension
+        ex = ModelEx(int(hp.get("n_ff_shexp", 0)), int(hp.get("moe_norm_w", 1)))
+        _chk(_L.kcpp_engine_bench_ex(ctypes.byref(h), ctypes.byref(ex), t, len(types), n_dev, ts, seed, n_prompt, ubatch,
+                                     n_warm, n_steps, out), "engine_bench_ex")
+    else:
+        _chk(_L.kcpp_engine_bench(ctypes.byref(h), t, len(types), n_dev, ts, seed, n_prompt, ubatch, n_warm, n_steps, out),
+             "engine_bench")
     return {"prefill_s": out[0], "decode_s": out[1], "n_past": int(out[2]), "rccl": bool(out[3])}
 
 
@@ -313,10 +328,16 @@ class Model:
         self._h = hparams(hp)
         self._t = (ctypes.c_int * len(types))(*types)
         il1 = hp["n_layer"] if il1 is None else il1
-        self.m = _L.kcpp_model_create(ctypes.byref(self._h), self._t, device, il0, il1, int(has_embed),
-                                      int(has_output), max_ubatch)
+        if "n_ff_shexp" in hp or "moe_norm_w" in hp:      # qwen2moe: a shared expert, raw top-k weights
+            self._ex = ModelEx(int(hp.get("n_ff_shexp", 0)), int(hp.get("moe_norm_w", 1)))
+            self.m = _L.kcpp_model_create_ex(ctypes.byref(self._h), ctypes.byref(self._ex), self._t, device, il0, il1,
+                                             int(has_embed), int(has_output), max_ubatch)
+        else:
+            self.m = _L.kcpp_model_create(ctypes.byref(self._h), self._t, device, il0, il1, int(has_embed),
+                                          int(has_output), max_ubatch)
         if not self.m:
-            raise KcppError("kcpp_model_create failed: %s" % (_L.kcpp_last_error() or b"").decode())
+            raise KcppError("kcpp_model_create%s failed: %s" % ("_ex" if hasattr(self, "_ex") else "",
+                                                                (_L.kcpp_last_error() or b"").decode()))
 
     def kv_shift(self, p0, diff, n_past):
         """context shift: cache rows [p0+diff, n_past) -> [p0, n_past-diff), K re-rotated by -diff"""
