@@ -121,6 +121,8 @@ int kcpp_gemv_rs(int type, const void *args, int mode, int pro, void *stream);
 /* q|k|v decode projection (mode 2, rms_norm + Q8_K prologue) with segments 0, 1 (q, k) in KT_Q4_K_RS and segment 2
  * (v) in KT_Q6_K_RS -- the Q4_K_M "more bits" layers -- in one launch; -3 when the shape is not covered */
 int kcpp_gemv_rs_qkv_mixed(const void *args, void *stream);
+/* the same with the prologue named: pro 1 = rms_norm (the call above), 3 = LayerNorm (kcpp_layer_norm; no bias / NeoX) */
+int kcpp_gemv_rs_qkv_mixed_pro(const void *args, int pro, void *stream);
 /* decode q|k|v with q in an RS layout (Q4_K / Q5_K / Q6_K, qargs) and k|v in Q8_0 (kvargs) -- Mixtral's Q5_K_M
  * policy -- as one grid holding both mat-vec launches' workgroups (mode 2 each, results identical to the two
  * kcpp_gemv_dec calls); -3 when not covered */
@@ -136,6 +138,9 @@ int kcpp_gemv_dec_plan(int entry, int type, int64_t K, int nseg, int64_t N0, int
 /* the same for kcpp_gemv_rs_qkv_mixed: out = {rc, NIA, NIB, MC, EX, block, nblk, lds_bytes} */
 int kcpp_gemv_qkv_mixed_plan(int64_t K, int64_t N0, int64_t N1, int64_t N2, int role0, int role1, int role2, int D,
                              int flags, int32_t out[8]);
+/* kcpp_gemv_rs_qkv_mixed_pro's (pro 1 / 3): out = {rc, NIA, NIB, MC, EX, block, nblk, lds_bytes, PRO} */
+int kcpp_gemv_qkv_mixed_plan_pro(int64_t K, int64_t N0, int64_t N1, int64_t N2, int role0, int role1, int role2, int D,
+                                 int flags, int pro, int32_t out[9]);
 /* and for kcpp_gemv_qkv_dual (q: nseg_a segments Na of qtype; k|v: nseg_b segments Nb of Q8_0):
  * out = {rc, nblk, lds_bytes, q half nblk, lds_bytes, NI, k|v half nblk, lds_bytes, IT} */
 int kcpp_gemv_qkv_dual_plan(int qtype, int64_t Ka, int nseg_a, const int64_t *Na, int flags_a, int64_t Kb, int nseg_b,
@@ -155,6 +160,16 @@ int kcpp_gemm_rms_norm(int type, const void *W, int64_t K, int64_t N, const void
 int kcpp_gemm_q6p_rms_norm(const void *img, const void *W, int64_t K, int64_t N, const void *act, int64_t M, float *Y,
                            int64_t ldy, const float *res, int64_t ldr, void *ws, void *stream, const float *norm_w, float eps,
                            void *q8k_out);
+/* LayerNorm without a bias times w, in ggml_compute_forward_norm_f32's order (two passes: mean = (float)(sum (double)x
+ * / ne0), v = x - mean in f32, var = (float)(sum (double)(v v) / ne0), y = (v / sqrtf(var + eps)) w), with
+ * kcpp_rms_norm's signature: y (f32) and / or q8k_out (= kcpp_layer_norm then kcpp_quantize_act(Q8_K), byte for byte).
+ * kcpp_layer_norm_q80: the Q8_0 activation (tile != 0: the KT_Q8_0_TA one), as kcpp_rms_norm_q80 / _q80t. */
+int kcpp_layer_norm(const float *x, int64_t ldx, const float *w, float *y, int64_t ldy, void *q8k_out, int64_t ne0,
+                    int64_t nrows, float eps, void *stream);
+int kcpp_layer_norm_q80(const float *x, int64_t ldx, const float *w, void *q80_out, int64_t ne0, int64_t nrows, float eps,
+                        int tile, void *stream);
+/* y[i] *= sc in place, one f32 multiply each (ggml_vec_scale_f32) */
+int kcpp_scale(float *y, float sc, int64_t n, void *stream);
 /* rms_norm * w quantized to Q8_0 in the same pass (= kcpp_rms_norm then kcpp_quantize_act(Q8_0), bit for bit) */
 int kcpp_rms_norm_q80(const float *x, int64_t ldx, const float *w, void *q80_out, int64_t ne0, int64_t nrows, float eps,
                       void *stream);
@@ -570,6 +585,17 @@ int kcpp_model_set_rope_mode(kcpp_model *m, int mode);
  * layer's bias; otherwise all three are required.  il must be a layer this stage owns.  Synchronous; drops captured
  * decode graphs. */
 int kcpp_model_set_qkv_bias(kcpp_model *m, int il, const float *bq, const float *bk, const float *bv);
+/* The Command-R class (build_command_r, src/llama.cpp:13986).  Each setter is called after kcpp_model_create and before
+ * the first decode, is synchronous and drops captured decode graphs.
+ * norm_mode 1: attn_norm and output_norm are LayerNorm without a bias (ggml_norm then ggml_mul; kcpp_layer_norm), and
+ * kcpp_hparams.eps then means layer_norm_epsilon; 0 (default): RMS norm.
+ * parallel_block 1: attention and the FFN both read attn_norm(x) and the layer output is (ffn_out + x) + attn_out;
+ * the layer's ffn_norm (entry 5 of the per-layer order) is unused and needs no upload.  Dense FFNs only.
+ * logit_scale: every logit is multiplied by it where the head writes them (ggml_scale), so the device argmax, the
+ * candidate front end and the host read all see scaled values; 0 or 1 = none. */
+int kcpp_model_set_norm_mode(kcpp_model *m, int mode);
+int kcpp_model_set_parallel_block(kcpp_model *m, int on);
+int kcpp_model_set_logit_scale(kcpp_model *m, float scale);
 /* koboldcpp's automatic RoPE base for a context beyond the trained one (CalcGradientAIRopeFreqBase,
  * gpttype_adapter.cpp:1598-1640); solar = the reference's ARCH_SOLAR rule (model_adapter.cpp:309) */
 float kcpp_gradient_ai_rope_base(float original_rope_base, int n_ctx_train, int n_ctx_desired, int solar);

@@ -873,8 +873,12 @@ bool load_model(const load_model_inputs inputs) {
     // expert behind a sigmoid gate in every layer
     const bool qmoe = arch == "qwen2moe";
     const bool qwen2 = arch == "qwen2" || qmoe;
+    // command-r (build_command_r, :13986-14133): LayerNorm without a bias for attn_norm / output_norm, no ffn_norm -- the
+    // FFN reads attn_norm(x) beside the attention and the layer is (ffn + x) + attn -- NORM rope pairs, tied embeddings,
+    // logits times logit_scale.  Command-R+ (per-head q / k LayerNorm, GQA 12) is refused below
+    const bool cmdr = arch == "command-r";
     const std::string pfx = arch + ".";
-    if (arch != "llama" && !qwen2) { fprintf(stderr, "[kcpp] load_model: architecture '%s' not supported\n", arch.c_str()); return false; }
+    if (arch != "llama" && !qwen2 && !cmdr) { fprintf(stderr, "[kcpp] load_model: architecture '%s' not supported\n", arch.c_str()); return false; }
     if (!e->tok.init(f, err)) { fprintf(stderr, "[kcpp] load_model: %s\n", err.c_str()); return false; }
     const gguf::Tensor *emb = f.tensor("token_embd.weight");
     if (!emb) { fprintf(stderr, "[kcpp] load_model: no token_embd.weight\n"); return false; }
@@ -886,6 +890,14 @@ bool load_model(const load_model_inputs inputs) {
     hp.n_head = (int)f.get_i(pfx + "attention.head_count", 0);
     hp.n_head_kv = (int)f.get_i(pfx + "attention.head_count_kv", hp.n_head);
     hp.eps = (float)f.get_f(pfx + "attention.layer_norm_rms_epsilon", 1e-5);
+    float logit_scale = 0.0f;
+    if (cmdr) {
+        // both keys are required ones in the reference (llm_load_hparams, src/llama.cpp:5904-5912)
+        for (const char *key : {"attention.layer_norm_epsilon", "logit_scale"})
+            if (!f.get(pfx + key)) { fprintf(stderr, "[kcpp] load_model: missing key %s%s\n", pfx.c_str(), key); return false; }
+        hp.eps = (float)f.get_f(pfx + "attention.layer_norm_epsilon", 1e-5);
+        logit_scale = (float)f.get_f(pfx + "logit_scale", 0.0);
+    }
     // RoPE (gpttype_adapter.cpp:1677-1700, 1926-1950): a user --ropeconfig (rope_freq_scale > 0) wins; a model that
     // sets its own RoPE (freq_base not 10000 / 500000, a linear scale, or YaRN) keeps its values; otherwise the base
     // is auto-scaled for the requested context by the GradientAI rule (CalcGradientAIRopeFreqBase)
@@ -901,7 +913,7 @@ bool load_model(const load_model_inputs inputs) {
     }
     const int n_ctx_train = (int)f.get_i(pfx + "context_length", 2048);     // FileFormatExtraMeta default
     // ARCH_SOLAR (model_adapter.cpp:309): llama, freq_base 10000, 435 or 611 tensors
-    const bool solar = !qwen2 && base_train == 10000.0f && (f.tensors.size() == 435 || f.tensors.size() == 611);
+    const bool solar = !qwen2 && !cmdr && base_train == 10000.0f && (f.tensors.size() == 435 || f.tensors.size() == 611);
     if (inputs.rope_freq_scale > 0.0f) {
         hp.rope_base = inputs.rope_freq_base;
         hp.rope_freq_scale = inputs.rope_freq_scale;
@@ -927,6 +939,38 @@ bool load_model(const load_model_inputs inputs) {
             return false;
         }
         if (!qmoe && f.get_i(pfx + "expert_count", 0) > 0) { fprintf(stderr, "[kcpp] load_model: qwen2 with experts is not supported\n"); return false; }
+    }
+    if (cmdr) {
+        // shapes and variants no kernel takes are refused here, never at a launch
+        const int hkv = hp.n_head_kv;
+        if (hp.n_layer >= 64) {
+            fprintf(stderr, "[kcpp] load_model: %sblock_count %d: Command-R+ (per-head q / k LayerNorm, GQA 12) is not supported\n",
+                    pfx.c_str(), hp.n_layer);
+            return false;
+        }
+        for (int il = 0; il < hp.n_layer; ++il)
+            for (const char *nm : {"attn_q_norm", "attn_k_norm"}) {
+                const std::string name = "blk." + std::to_string(il) + "." + nm + ".weight";
+                if (f.tensor(name)) {
+                    fprintf(stderr, "[kcpp] load_model: %s: per-head q / k LayerNorm (Command-R+) is not supported\n", name.c_str());
+                    return false;
+                }
+            }
+        if (hkv < 1 || hp.n_head % hkv || hp.n_head / hkv > 8 || hp.n_embd % hp.n_head) {
+            fprintf(stderr, "[kcpp] load_model: %sattention.head_count %d / %sattention.head_count_kv %d: need whole GQA "
+                            "groups of at most 8 query heads\n", pfx.c_str(), hp.n_head, pfx.c_str(), hkv);
+            return false;
+        }
+        if (!f.tensor("output.weight") && (emb->type == KT_F32 || emb->type == KT_F16)) {
+            fprintf(stderr, "[kcpp] load_model: token_embd.weight: an F32 / F16 embedding cannot serve as the tied output head "
+                            "(no mat-vec kernel for the type)\n");
+            return false;
+        }
+        if (f.get_i(pfx + "expert_count", 0) > 0) {
+            fprintf(stderr, "[kcpp] load_model: %sexpert_count %d: command-r with experts is not supported\n", pfx.c_str(),
+                    (int)f.get_i(pfx + "expert_count", 0));
+            return false;
+        }
     }
     // mixture of experts (llm_load_hparams / llm_load_tensors, src/llama.cpp:5444-5445, 7176-7215)
     hp.n_expert = (int)f.get_i(pfx + "expert_count", 0);
@@ -977,6 +1021,7 @@ bool load_model(const load_model_inputs inputs) {
         const std::string b = "blk." + std::to_string(il) + ".";
         for (int j = 0; j < 9; ++j) {
             const int k = 3 + LW * il + j;
+            if (cmdr && j == 5) continue;            // no ffn_norm: the entry stays empty and gets no upload
             if (hp.n_expert == 0 || j < 6) { set(k, f.tensor(b + tname(il, j) + ".weight")); continue; }
             set(k, f.tensor(b + exps[j - 6] + ".weight"));
             if (ts[k].t) {
@@ -1027,6 +1072,7 @@ bool load_model(const load_model_inputs inputs) {
     }
     e->types.resize(ts.size());
     for (size_t k = 0; k < ts.size(); ++k) {
+        if (cmdr && k >= 3 && (k - 3) % LW == 5) { e->types[k] = KT_F32; continue; }
         if (!ts[k].t) { fprintf(stderr, "[kcpp] load_model: missing tensor #%zu\n", k); return false; }
         if (!supported_type(ts[k].type)) {
             fprintf(stderr, "[kcpp] load_model: tensor %s has unsupported type %d\n", ts[k].t->name.c_str(), ts[k].type);
@@ -1037,10 +1083,10 @@ bool load_model(const load_model_inputs inputs) {
     // qwen2: blk.N.attn_{q,k,v}.bias, all three required, F32 with n_embd / n_embd_gqa / n_embd_gqa values
     // (llm_load_tensors, src/llama.cpp:7739-7777); every matrix row must be whole blocks of its type
     std::vector<const float *> qkv_bias;
-    if (qwen2) {
+    if (qwen2 || cmdr) {
         const int64_t ekv = (int64_t)hp.n_head_kv * (hp.n_embd / hp.n_head);
         for (size_t k = 0; k < ts.size(); ++k)
-            if (ts[k].t->ne[0] % ks_block_elems(ts[k].type)) {
+            if (ts[k].t && ts[k].t->ne[0] % ks_block_elems(ts[k].type)) {
                 fprintf(stderr, "[kcpp] load_model: %s: row length %lld is not a multiple of the type's block\n",
                         ts[k].t->name.c_str(), (long long)ts[k].t->ne[0]);
                 return false;
@@ -1051,6 +1097,14 @@ bool load_model(const load_model_inputs inputs) {
                 const std::string name = "blk." + std::to_string(il) + "." + bn[j];
                 const gguf::Tensor *bt = f.tensor(name);
                 const int64_t want = j == 0 ? hp.n_embd : ekv;
+                if (cmdr && !bt) {
+                    // optional in build_command_r; a layer has all three or none
+                    bool any = false;
+                    for (int q = 0; q < 3; ++q) any |= f.tensor("blk." + std::to_string(il) + "." + bn[q]) != nullptr;
+                    if (any) { fprintf(stderr, "[kcpp] load_model: %s: missing tensor (a layer needs all of attn_q / attn_k / attn_v .bias, or none)\n", name.c_str()); return false; }
+                    qkv_bias.push_back(nullptr);
+                    continue;
+                }
                 if (!bt || bt->type != KT_F32 || bt->ne[0] != want || bt->ne[1] * bt->ne[2] * bt->ne[3] != 1) {
                     fprintf(stderr, "[kcpp] load_model: %s: %s (expected %lld F32 values)\n", name.c_str(),
                             bt ? "wrong type or length" : "missing tensor", (long long)want);
@@ -1086,6 +1140,10 @@ bool load_model(const load_model_inputs inputs) {
     if (getenv("KCPP_VIRTUAL_DEVICES")) ndev = std::max(1, atoi(getenv("KCPP_VIRTUAL_DEVICES")));
     e->ub = inputs.blasbatchsize > 0 ? std::min(inputs.blasbatchsize, 512) : 512;
     e->use_contextshift = inputs.use_contextshift;
+    if (cmdr && inputs.use_rowsplit && std::min(ndev, KCPP_TENSOR_SPLIT_MAX) > 1) {
+        fprintf(stderr, "[kcpp] load_model: command-r: row split is not supported (use the layer split)\n");
+        return false;
+    }
     if (!build_stages(*e, ndev, nreal, inputs.tensor_split, inputs.use_rowsplit, inputs.cublas_info)) return false;
     if (!init_handoff(*e)) { fprintf(stderr, "[kcpp] load_model: handoff events\n"); return false; }
     // KV cache types (gpttype_adapter.cpp:1958-1959: quant_k/v > 1 -> Q4_0, == 1 -> Q8_0, else F16).  Quantized
@@ -1108,11 +1166,17 @@ bool load_model(const load_model_inputs inputs) {
                 fprintf(stderr, "[kcpp] load_model: rope_freqs: %s\n", kcpp_last_error());
                 return false;
             }
-    if (qwen2)       // NeoX pairs (llama_rope_type, src/llama.cpp:19731) and the biases, on every stage for its layers
+    if (cmdr)        // LayerNorm, the parallel block and the logit scale, on every stage
+        for (kcpp_model *m : e->stages)
+            if (kcpp_model_set_norm_mode(m, 1) || kcpp_model_set_parallel_block(m, 1) || kcpp_model_set_logit_scale(m, logit_scale)) {
+                fprintf(stderr, "[kcpp] load_model: command-r: %s\n", kcpp_last_error());
+                return false;
+            }
+    if (qwen2 || cmdr)   // NeoX pairs (llama_rope_type, src/llama.cpp:19731) and the biases, on every stage for its layers
         for (kcpp_model *m : e->stages) {
-            if (kcpp_model_set_rope_mode(m, 2)) { fprintf(stderr, "[kcpp] load_model: rope mode: %s\n", kcpp_last_error()); return false; }
+            if (qwen2 && kcpp_model_set_rope_mode(m, 2)) { fprintf(stderr, "[kcpp] load_model: rope mode: %s\n", kcpp_last_error()); return false; }
             for (int il = 0; il < hp.n_layer; ++il) {
-                if (!kcpp_model_owns_layer(m, il)) continue;
+                if (!kcpp_model_owns_layer(m, il) || !qkv_bias[3 * il]) continue;
                 if (kcpp_model_set_qkv_bias(m, il, qkv_bias[3 * il], qkv_bias[3 * il + 1], qkv_bias[3 * il + 2])) {
                     fprintf(stderr, "[kcpp] load_model: blk.%d q/k/v bias: %s\n", il, kcpp_last_error());
                     return false;
@@ -1120,6 +1184,7 @@ bool load_model(const load_model_inputs inputs) {
             }
         }
     for (size_t k = 0; k < ts.size(); ++k) {
+        if (!ts[k].t) continue;                       // command-r's unused ffn_norm entry
         for (kcpp_model *m : e->stages)
             if (kcpp_model_set_tensor(m, (int)k, ts[k].data, ts[k].bytes)) {
                 fprintf(stderr, "[kcpp] load_model: upload %s: %s\n", ts[k].t->name.c_str(), kcpp_last_error());

@@ -53,6 +53,16 @@ extern "C" int kcpp_gemv_qkv_mixed_plan(int64_t K, int64_t N0, int64_t N1, int64
     for (int i = 0; i < 8; ++i) out[i] = v[i];
     return m.rc;
 }
+// the same for kcpp_gemv_rs_qkv_mixed_pro (pro 1 / 3): out = {rc, NIA, NIB, MC, EX, block, nblk, lds_bytes, PRO}
+extern "C" int kcpp_gemv_qkv_mixed_plan_pro(int64_t K, int64_t N0, int64_t N1, int64_t N2, int role0, int role1, int role2, int D,
+                                            int flags, int pro, int32_t out[9]) {
+    const GemvShape s{KT_Q4_K_RS, K, 3, {N0, N1, N2}, {role0, role1, role2}, D, 2, pro, 2, flags, 0, 0};
+    GemvMixedPlan m;
+    gemv_qkv_mixed_plan(s, &m);
+    const int32_t v[9] = {m.rc, m.NIA, m.NIB, m.MC, m.EX, m.block, (int32_t)m.nblk, (int32_t)m.lds_bytes, m.PRO};
+    for (int i = 0; i < 9; ++i) out[i] = v[i];
+    return m.rc;
+}
 // Dual (kcpp_gemv_qkv_dual; q of nseg_a segments Na in qtype, k|v of nseg_b segments Nb in Q8_0):
 // out = {rc, nblk, lds_bytes, a.nblk, a.lds_bytes, a.NI, b.nblk, b.lds_bytes, b.IT}
 extern "C" int kcpp_gemv_qkv_dual_plan(int qtype, int64_t Ka, int nseg_a, const int64_t *Na, int flags_a, int64_t Kb, int nseg_b,

@@ -14,10 +14,13 @@ namespace lean {
 // NT threads per workgroup (MAXC = 16-element chunks per thread: ceil(K / (16 NT)))
 // STORE (the ggml plugin's RMS_NORM -> MUL fused into the first consumer, AUX instances): compute() also stores the
 // normalised row r = x * scale and the product y = r * w (the two nodes' tensors) where given
+// PRO 3 (the Command-R class): LayerNorm in ggml_compute_forward_norm_f32's order in place of the RMS norm -- mean =
+// (float)(sum (double)x / K), v = x - mean in f32, var = (float)(sum (double)(v v) / K), y = (v / sqrt(var + eps)) w --
+// with PRO 1's thread -> element map and double wave / workgroup sums; one workgroup reduction (and barrier) more
 template <int PRO, int MAXC, int NT = 256, bool STORE = false>
 struct ActPro {               // rms_norm * w -> Q8_K into LDS (see gemv_dec_impl.h); loads first
     float v[MAXC][16];
-    float w[PRO == 1 ? MAXC : 1][16];
+    float w[PRO == 1 || PRO == 3 ? MAXC : 1][16];
     __device__ __forceinline__ void load(const DecArgs &a, int64_t xoff = 0) {   // input row a.x + xoff
         const int tid = threadIdx.x, nchunk = (int)(a.K / 16);
 #pragma unroll
@@ -29,7 +32,7 @@ struct ActPro {               // rms_norm * w -> Q8_K into LDS (see gemv_dec_imp
                 const float4 f = p[k];
                 v[i][4 * k] = f.x; v[i][4 * k + 1] = f.y; v[i][4 * k + 2] = f.z; v[i][4 * k + 3] = f.w;
             }
-            if constexpr (PRO == 1) {
+            if constexpr (PRO == 1 || PRO == 3) {
                 const float4 *q = (const float4 *)(a.nw + 16 * (int64_t)c);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
@@ -100,6 +103,45 @@ struct ActPro {               // rms_norm * w -> Q8_K into LDS (see gemv_dec_imp
 #pragma unroll
                     for (int e = 0; e < 16; ++e) v[i][e] = __fmul_rn(__fmul_rn(v[i][e], scale), w[i][e]);
             }
+        }
+        if constexpr (PRO == 3) {
+            static_assert(!STORE, "PRO 3: no AUX instances");
+            __shared__ double red_m[NT / 64], red_v[NT / 64];
+            double sm = 0.0;
+#pragma unroll
+            for (int i = 0; i < MAXC; ++i)
+                if (tid + NT * i < nchunk) {
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) sm += (double)v[i][e];
+                }
+            sm = wave_sum_d(sm);
+            if ((tid & 63) == 0) red_m[tid >> 6] = sm;
+            __syncthreads();
+            double sum = red_m[0] + red_m[1] + red_m[2] + red_m[3];
+#pragma unroll
+            for (int i = 4; i < NT / 64; i += 4) sum += red_m[i] + red_m[i + 1] + red_m[i + 2] + red_m[i + 3];
+            const float mean = (float)(sum / (double)K);                           // ggml.c:12019
+            double ss = 0.0;
+#pragma unroll
+            for (int i = 0; i < MAXC; ++i) {
+#pragma unroll
+                for (int e = 0; e < 16; ++e) v[i][e] = __fsub_rn(v[i][e], mean);
+                if (tid + NT * i < nchunk) {
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) ss += (double)__fmul_rn(v[i][e], v[i][e]);
+                }
+            }
+            ss = wave_sum_d(ss);
+            if ((tid & 63) == 0) red_v[tid >> 6] = ss;
+            __syncthreads();
+            double sum2 = red_v[0] + red_v[1] + red_v[2] + red_v[3];
+#pragma unroll
+            for (int i = 4; i < NT / 64; i += 4) sum2 += red_v[i] + red_v[i + 1] + red_v[i + 2] + red_v[i + 3];
+            const float scale = 1.0f / sqrtf((float)(sum2 / (double)K) + a.eps);   // ggml.c:12030
+#pragma unroll
+            for (int i = 0; i < MAXC; ++i)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) v[i][e] = __fmul_rn(__fmul_rn(v[i][e], scale), w[i][e]);
         }
         int8_t *qs = (int8_t *)lds;
         float *d = (float *)(lds + K);

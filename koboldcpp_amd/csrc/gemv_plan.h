@@ -44,7 +44,11 @@
 //   Q6_K 13.6 -> 12.2 (no PF: two rows per wave, both in flight), wo 5.4 -> 4.7; in the bench's token graph down 12.0 /
 //   13.7 -> 10.0 / 12.4, wo 5.3 -> 5.1, GLU unchanged: 577 -> 600 tok/s.  q|k|v stays at 4 waves (8: 6.8 -> 7.4 us,
 //   592 tok/s).  A router on that GLU (ROUTE): two segments, 2..8 experts, K <= 4096, F32 / F16 router weight, ids and
-//   weights outputs given, else -3.  Any pro outside 0..2: -3.  A mode outside 0..3 runs the table as mode 0.
+//   weights outputs given, else -3.  Any pro outside 0..3: -3.  A mode outside 0..3 runs the table as mode 0.
+//   pro 3 (LayerNorm prologue, the Command-R class): dense weights (no eid, eid1, escale, router), no ex, no aux, not XL,
+//     and one of: mode 2 (R 2, 4 waves, cap 512); mode 1 with one segment (R 1, PF, 8 waves, cap 256); mode 0 with one
+//     segment of more than 16384 rows, the head (R 2, 4 waves, cap 512) -- pro 1's plans of the same shapes.  Else -3,
+//     and -3 from every other family (GEMV_Q4K, GEMV_STREAM, GEMV_UNIT) and the mixed launch with ex.
 //   A segment whose rows are no multiple of R: -5.
 // GEMV_RS_AUX (k_gemv_rs_aux, the ggml plugin's fused nodes; kcpp_gemv_rs_aux)
 //   An AuxOut; mode 0 with p0, h0 or a rope, or mode 1 with the GLU triple; a rope only in mode 0, with positions and an
@@ -249,6 +253,10 @@ inline int gemv_rs_plan(const GemvShape &s, bool aux_entry, GemvPlan *p) {
             }
         }
         if (!gemv_rs_class(s.type, s.K, p)) return -3;
+        if (pro == 3) {
+            if (aux_entry || p->XL || ex || route || (f & (GEMV_F_EID | GEMV_F_EID1 | GEMV_F_ESCALE))) return -3;
+            if (!(mode == 2 || (mode == 1 && s.nseg == 1) || (mode == 0 && s.nseg == 1 && rows > 16384))) return -3;
+        }
         if (p->XL) {
             if (aux_entry || (mode == 2 && ex)) return -3;
             if (mode == 0 ? pro < 0 || pro > 2 : (mode == 1 ? pro != 0 && pro != 1 : (mode == 2 ? pro != 1 : true))) return -3;
@@ -276,7 +284,7 @@ inline int gemv_rs_plan(const GemvShape &s, bool aux_entry, GemvPlan *p) {
                 } else {
                     return -3;
                 }
-            } else if (mode == 1 && pro == 1) {
+            } else if (mode == 1 && (pro == 1 || pro == 3)) {
                 if (route) {
                     if (p->MC != 1 || s.nseg != 2 || s.route_ne < 2 || s.route_ne > 8 || s.K > 4096 || !(f & GEMV_F_ROUTE_OUT) ||
                         (s.route_wt != KT_F32 && s.route_wt != KT_F16))
@@ -286,7 +294,7 @@ inline int gemv_rs_plan(const GemvShape &s, bool aux_entry, GemvPlan *p) {
                 p->waves = 8, cap = 256;
             } else if (mode == 0 && pro == 2 && rows <= 16384) {
                 p->PF = 0, p->waves = 8, cap = 256;
-            } else if (pro < 0 || pro > 2) {
+            } else if (pro < 0 || pro > 3) {
                 return -3;
             }
         }
@@ -360,6 +368,8 @@ inline int gemv_unit_plan(const GemvShape &s, GemvPlan *p) {
 // what the entry runs for the shape; the return value is p->rc
 inline int gemv_plan(const GemvShape &s, int entry, GemvPlan *p) {
     *p = GemvPlan{};
+    // pro 3 (LayerNorm): instances of the RS kernels only
+    if (s.pro == 3 && !((entry == GEMV_ENTRY_RS || entry == GEMV_ENTRY_DEC) && gemv_rs_type(s.type))) return p->rc = -3;
     switch (entry) {
     case GEMV_ENTRY_RS: p->rc = gemv_rs_plan(s, false, p); break;
     case GEMV_ENTRY_RS_AUX: p->rc = gemv_rs_plan(s, true, p); break;
@@ -388,6 +398,7 @@ inline int gemv_plan(const GemvShape &s, int entry, GemvPlan *p) {
 struct GemvMixedPlan {
     int rc;
     int NIA, NIB, MC, EX;
+    int PRO;                     // 1: rms_norm prologue, 3: LayerNorm (s.pro == 3; not with ex)
     int64_t nblk;
     int block;
     int64_t lds_bytes;
@@ -401,6 +412,8 @@ inline int gemv_qkv_mixed_plan(const GemvShape &s, GemvMixedPlan *m) {
     // ex: segments 0, 1 = q, k and 2 = v as the runtime passes them; whole heads
     if (ex && (s.role[0] != 0 || s.role[1] != 1 || s.role[2] != 2)) return m->rc;
     if (ex && (s.flags & GEMV_F_NEOX) && (s.D < 2 || s.D % 2 || s.N[0] % s.D || s.N[1] % s.D)) return m->rc;
+    if (s.pro == 3 && ex) return m->rc;
+    m->PRO = s.pro == 3 ? 3 : 1;
     GemvPlan a{}, b{};
     gemv_rs_class(KT_Q4_K_RS, s.K, &a);
     gemv_rs_class(KT_Q6_K_RS, s.K, &b);

@@ -49,7 +49,8 @@ using namespace rs;
 
 
 // NI = pieces per lane per row (ceil(nsb * PIECES_PER_SB / 64)); R rows per group (x2 for gate|up);
-// PRO 0: act copy, 1: rms_norm * w -> Q8_K, 2: quantize only; MC = ceil(K / 4096) prologue chunks;
+// PRO 0: act copy, 1: rms_norm * w -> Q8_K, 2: quantize only, 3: LayerNorm * w -> Q8_K (the Command-R class: q|k|v,
+// the 8-wave gate|up and the head only -- instances of their own, the PRO 1 / 2 ones are the code they were); MC = ceil(K / 4096) prologue chunks;
 // PF: issue the next group's loads before reducing the current one.
 // NWV waves per workgroup (4, or 8: one activation prologue shared by twice the waves)
 // XL (long K: 70B ffn_down K = 28672, MoE n_ff > 14336): the lane's activation slices are read from the LDS image per
@@ -112,7 +113,8 @@ namespace {
     X(1, 0, PRO_, 0, 4, false, false)
 #define KCPP_RS_INSTANCES(X)                                                                                          \
     KCPP_RS_BY_PRO(X, 0) KCPP_RS_BY_PRO(X, 1) KCPP_RS_BY_PRO(X, 2)                                                     \
-    X(1, 1, 1, 1, 8, false, false) X(1, 0, 2, 0, 8, false, false) X(2, 2, 1, 0, 4, false, true)
+    X(1, 1, 1, 1, 8, false, false) X(1, 0, 2, 0, 8, false, false) X(2, 2, 1, 0, 4, false, true)                        \
+    X(2, 2, 3, 0, 4, false, false) X(1, 1, 3, 1, 8, false, false) X(2, 0, 3, 0, 4, false, false)
 #define KCPP_RS_AUX_INSTANCES(X) X(2, 0, 2, 0, 4) X(2, 0, 1, 0, 4) X(1, 0, 2, 0, 8) X(1, 1, 2, 1, 4) X(1, 1, 1, 1, 8)
 // long K (XL, NI a ceiling, 8 waves, no prefetch): (R, MODE, PRO)
 #define KCPP_RS_XL_INSTANCES(X) X(1, 0, 2) X(1, 0, 1) X(1, 0, 0) X(1, 1, 1) X(1, 1, 0) X(2, 2, 1)
@@ -187,7 +189,8 @@ int gemv_rs_launch(const GemvPlan &p, const DecArgs &a, const AuxOut *o, hipStre
 // kernel of its own: prologue, one group per wave, epilogue), segments 0 / 1 (q, k) run the Q4_K_RS path and
 // segment 2 (v) the Q6_K_RS path of one grid over the same LDS activation (rms_norm -> Q8_K prologue, both types'
 // vec_dot_type); groups are wave-uniform in type.  Mode 2 epilogue (RoPE + f16 q / K / V stores), R = 2.
-template <int NIA, int NIB, int MC, bool EX = false>
+// PRO: 1 = rms_norm, 3 = LayerNorm (lean::ActPro)
+template <int NIA, int NIB, int MC, bool EX = false, int PRO = 1>
 __global__ void __launch_bounds__(256) k_gemv_rs_qkv(const int kb_nblk, const DecArgs a) {   // kb_nblk: see k_gemv_rs
     using TA = RS<KT_Q4_K_RS>;
     using TB = RS<KT_Q6_K_RS>;
@@ -239,7 +242,7 @@ __global__ void __launch_bounds__(256) k_gemv_rs_qkv(const int kb_nblk, const De
     BufA ba;
     BufB bb;
     const int g0 = min(wid, ngroups - 1);
-    lean::ActPro<1, MC> pro;
+    lean::ActPro<PRO, MC> pro;
     pro.load(a);
     if (g0 < ngA) issueA(g0, ba);
     else issueB(g0, bb);
@@ -287,13 +290,15 @@ __global__ void __launch_bounds__(256) k_gemv_rs_qkv(const int kb_nblk, const De
 }
 
 // q|k|v decode projection with q, k in Q4_K_RS and v in Q6_K_RS (segments 0, 1, 2): one launch.  -3 when not covered.
-extern "C" int kcpp_gemv_rs_qkv_mixed(const void *args, void *stream) {
+// pro: 1 = rms_norm prologue, 3 = LayerNorm (no bias / NeoX instance: -3)
+extern "C" int kcpp_gemv_rs_qkv_mixed_pro(const void *args, int pro, void *stream) {
     const DecArgs &a = *(const DecArgs *)args;
     GemvMixedPlan m;
-    if (gemv_qkv_mixed_plan(gemv_shape_of(KT_Q4_K_RS, a, 2, 1, 2), &m)) return m.rc;
+    if (gemv_qkv_mixed_plan(gemv_shape_of(KT_Q4_K_RS, a, 2, pro, 2), &m)) return m.rc;
     void (*k)(int, const DecArgs) = nullptr;
 #define KCPP_QKVM(A_, B_, M_)                                                                                          \
-    if (m.NIA == A_ && m.NIB == B_ && m.MC == M_) k = m.EX ? k_gemv_rs_qkv<A_, B_, M_, true> : k_gemv_rs_qkv<A_, B_, M_>;
+    if (m.NIA == A_ && m.NIB == B_ && m.MC == M_)                                                                      \
+        k = m.PRO == 3 ? k_gemv_rs_qkv<A_, B_, M_, false, 3> : (m.EX ? k_gemv_rs_qkv<A_, B_, M_, true> : k_gemv_rs_qkv<A_, B_, M_>);
     KCPP_QKVM(2, 1, 1)          // n_embd 4096 (Llama-3-8B)
     KCPP_QKVM(4, 2, 2)          // n_embd 8192 (Llama-3-70B)
     KCPP_QKVM(1, 1, 1)
@@ -302,6 +307,7 @@ extern "C" int kcpp_gemv_rs_qkv_mixed(const void *args, void *stream) {
     void *ka[] = {&nblk, (void *)&a};
     return gemv_go((const void *)k, m.nblk, m.block, m.lds_bytes, ka, (hipStream_t)stream);
 }
+extern "C" int kcpp_gemv_rs_qkv_mixed(const void *args, void *stream) { return kcpp_gemv_rs_qkv_mixed_pro(args, 1, stream); }
 
 // ---------------------------------------------------------------- q (RS layout) + k|v (Q8_0) in one launch
 // Mixtral's Q5_K_M policy keeps attn_k / attn_v in Q8_0 (n_expert == 8) and attn_q in Q5_K, so its q|k|v decode step

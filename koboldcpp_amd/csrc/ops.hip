@@ -15,6 +15,10 @@
 // group is exactly one Q8_K super-block, so the fused quantization needs only DPP steps.
 // part (optional): x is first formed from KS split-K partials [KS][Mp][ne0] summed in split order plus res, exactly as
 // gemm.hip k_splitk_reduce does, and stored at xout -- the reduce and the norm of the next layer step in one launch
+// LN: LayerNorm without a bias (ggml_compute_forward_norm_f32, ggml.c:11988, then ggml_mul by w; build_command_r) -- the
+// row's mean (float)(sum (double)x / ne0) is subtracted in f32 first, the rest is the same code on v = x - mean: two
+// passes in the reference's order, never E[x^2] - mean^2
+template <bool LN>
 __global__ void __launch_bounds__(1024) k_rms_norm(const float *__restrict__ x, int64_t ldx, const float *__restrict__ w,
                                                    float *__restrict__ y, int64_t ldy, uint8_t *__restrict__ qout,
                                                    int64_t ne0, int64_t nrows, float eps, int q80 = 0,
@@ -49,6 +53,20 @@ __global__ void __launch_bounds__(1024) k_rms_norm(const float *__restrict__ x, 
             const float4 f = active ? src[k] : make_float4(0, 0, 0, 0);
             v[4 * k] = f.x; v[4 * k + 1] = f.y; v[4 * k + 2] = f.z; v[4 * k + 3] = f.w;
         }
+    }
+    if constexpr (LN) {
+        double sm = 0.0;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) sm += (double)v[e];
+        sm = wave_sum(sm);
+        __shared__ double red_m[16];
+        if (lane == 0) red_m[wave] = sm;
+        __syncthreads();
+        double tot = 0.0;
+        for (int i = 0; i < nw; ++i) tot += red_m[i];
+        const float mu = (float)(tot / (double)ne0);
+#pragma unroll
+        for (int e = 0; e < 16; ++e) v[e] = active ? __fsub_rn(v[e], mu) : 0.0f;
     }
     double ss = 0.0;
 #pragma unroll
@@ -183,6 +201,10 @@ __global__ void k_add(float *__restrict__ y, const float *__restrict__ a, const 
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) y[i] = __fadd_rn(a[i], b[i]);
 }
+__global__ void k_scale(float *__restrict__ y, float sc, int64_t n) {      // ggml_vec_scale_f32
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) y[i] = __fmul_rn(y[i], sc);
+}
 __global__ void k_silu_mul(float *__restrict__ y, const float *__restrict__ g, const float *__restrict__ u, int64_t n) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) { const float x = g[i]; y[i] = (x / (1.0f + expf(-x))) * u[i]; }
@@ -227,7 +249,7 @@ int kcpp_rms_norm(const float *x, int64_t ldx, const float *w, float *y, int64_t
                   int64_t nrows, float eps, void *stream) {
     if (ne0 % 256 || ne0 > 16384) return -1;
     const unsigned nthr = (unsigned)(ne0 / 16 < 64 ? 64 : ne0 / 16);
-    hipLaunchKernelGGL(k_rms_norm, dim3((unsigned)nrows), dim3(nthr), 0, (hipStream_t)stream, x, ldx, w, y,
+    hipLaunchKernelGGL(k_rms_norm<false>, dim3((unsigned)nrows), dim3(nthr), 0, (hipStream_t)stream, x, ldx, w, y,
                        ldy, (uint8_t *)q8k_out, ne0, nrows, eps);
     KCPP_CHECK(hipGetLastError());
     return 0;
@@ -239,7 +261,7 @@ int kcpp_reduce_rms_norm(const float *part, int KS, int64_t Mp, const float *res
                          const float *w, void *q8k_out, int64_t ne0, int64_t nrows, float eps, void *stream) {
     if (ne0 % 256 || ne0 > 16384 || !part || KS < 1 || !x || !q8k_out) return -1;
     const unsigned nthr = (unsigned)(ne0 / 16 < 64 ? 64 : ne0 / 16);
-    hipLaunchKernelGGL(k_rms_norm, dim3((unsigned)nrows), dim3(nthr), 0, (hipStream_t)stream, (const float *)x, ldx, w,
+    hipLaunchKernelGGL(k_rms_norm<false>, dim3((unsigned)nrows), dim3(nthr), 0, (hipStream_t)stream, (const float *)x, ldx, w,
                        (float *)nullptr, (int64_t)0, (uint8_t *)q8k_out, ne0, nrows, eps, 0, part, KS, Mp, x, res, ldr);
     KCPP_CHECK(hipGetLastError());
     return 0;
@@ -249,7 +271,7 @@ int kcpp_rms_norm_q80(const float *x, int64_t ldx, const float *w, void *q80_out
                       void *stream) {
     if (ne0 % 256 || ne0 > 16384 || !q80_out) return -1;
     const unsigned nthr = (unsigned)(ne0 / 16 < 64 ? 64 : ne0 / 16);
-    hipLaunchKernelGGL(k_rms_norm, dim3((unsigned)nrows), dim3(nthr), 0, (hipStream_t)stream, x, ldx, w, (float *)nullptr,
+    hipLaunchKernelGGL(k_rms_norm<false>, dim3((unsigned)nrows), dim3(nthr), 0, (hipStream_t)stream, x, ldx, w, (float *)nullptr,
                        (int64_t)0, (uint8_t *)q80_out, ne0, nrows, eps, 1);
     KCPP_CHECK(hipGetLastError());
     return 0;
@@ -260,8 +282,29 @@ int kcpp_rms_norm_q80t(const float *x, int64_t ldx, const float *w, void *q80t_o
                        void *stream) {
     if (ne0 % 256 || ne0 > 16384 || !q80t_out) return -1;
     const unsigned nthr = (unsigned)(ne0 / 16 < 64 ? 64 : ne0 / 16);
-    hipLaunchKernelGGL(k_rms_norm, dim3((unsigned)nrows), dim3(nthr), 0, (hipStream_t)stream, x, ldx, w, (float *)nullptr,
+    hipLaunchKernelGGL(k_rms_norm<false>, dim3((unsigned)nrows), dim3(nthr), 0, (hipStream_t)stream, x, ldx, w, (float *)nullptr,
                        (int64_t)0, (uint8_t *)q80t_out, ne0, nrows, eps, 2);
+    KCPP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// LayerNorm * w (no bias) with kcpp_rms_norm's signature and outputs: y (f32) and / or the Q8_K activation
+int kcpp_layer_norm(const float *x, int64_t ldx, const float *w, float *y, int64_t ldy, void *q8k_out, int64_t ne0,
+                    int64_t nrows, float eps, void *stream) {
+    if (ne0 % 256 || ne0 > 16384) return -1;
+    const unsigned nthr = (unsigned)(ne0 / 16 < 64 ? 64 : ne0 / 16);
+    hipLaunchKernelGGL(k_rms_norm<true>, dim3((unsigned)nrows), dim3(nthr), 0, (hipStream_t)stream, x, ldx, w, y, ldy,
+                       (uint8_t *)q8k_out, ne0, nrows, eps);
+    KCPP_CHECK(hipGetLastError());
+    return 0;
+}
+// ... -> the Q8_0 activation (tile: the KT_Q8_0_TA activation of KT_Q8_0_T weights), as kcpp_rms_norm_q80 / _q80t
+int kcpp_layer_norm_q80(const float *x, int64_t ldx, const float *w, void *q80_out, int64_t ne0, int64_t nrows, float eps,
+                        int tile, void *stream) {
+    if (ne0 % 256 || ne0 > 16384 || !q80_out) return -1;
+    const unsigned nthr = (unsigned)(ne0 / 16 < 64 ? 64 : ne0 / 16);
+    hipLaunchKernelGGL(k_rms_norm<true>, dim3((unsigned)nrows), dim3(nthr), 0, (hipStream_t)stream, x, ldx, w, (float *)nullptr,
+                       (int64_t)0, (uint8_t *)q80_out, ne0, nrows, eps, tile ? 2 : 1);
     KCPP_CHECK(hipGetLastError());
     return 0;
 }
@@ -311,6 +354,13 @@ int kcpp_kv_shift_rows(const uint16_t *kc, const uint16_t *vc, uint16_t *ks, uin
 
 int kcpp_add(float *y, const float *a, const float *b, int64_t n, void *stream) {
     hipLaunchKernelGGL(k_add, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y, a, b, n);
+    KCPP_CHECK(hipGetLastError());
+    return 0;
+}
+// y *= sc in place (ggml_scale: the Command-R logit scale)
+int kcpp_scale(float *y, float sc, int64_t n, void *stream) {
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(k_scale, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y, sc, n);
     KCPP_CHECK(hipGetLastError());
     return 0;
 }

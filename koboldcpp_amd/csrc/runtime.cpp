@@ -152,6 +152,10 @@ struct kcpp_model {
     float *moe_rw_h = nullptr;
     float2 *rope_tab = nullptr;
     int rope_mode = 0;                      // 0 = NORM pairs, 2 = NeoX pairs (kcpp_model_set_rope_mode)
+    // the Command-R class (build_command_r; kcpp_model_set_norm_mode / _parallel_block / _logit_scale)
+    int norm_mode = 0;                      // 1: attn_norm, ffn_norm and output_norm are LayerNorm (no bias); hp.eps its epsilon
+    bool parallel = false;                  // attention and the FFN both read attn_norm(x); x = (ffn + x) + attn
+    float logit_scale = 0.0f;               // logits times this where the head writes them; 0 or 1: none
     std::vector<float> rope_ff;             // rope frequency factors (rope_freqs.weight); empty: none
     void *kv_scratch = nullptr;             // context shift: moved K/V rows (n_ctx x EKV x 2 f16, lazily)
     float *shift_cs = nullptr;              // context shift: (cos, sin) pairs of the shift distance
@@ -344,6 +348,35 @@ extern "C" int kcpp_model_set_rope_mode(kcpp_model *m, int mode) {
     RT_CHECK(hipStreamSynchronize(m->stream));
     drop_graphs(m);
     m->rope_mode = mode;
+    return 0;
+}
+
+extern "C" int kcpp_model_set_norm_mode(kcpp_model *m, int mode) {
+    if (!m || (mode != 0 && mode != 1)) { g_err = "norm_mode: 0 (RMS norm) or 1 (LayerNorm)"; return -1; }
+    if (mode && m->hp.n_expert > 0) { g_err = "norm_mode: LayerNorm with a mixture of experts is not supported"; return -1; }
+    RT_CHECK(hipSetDevice(m->device));
+    RT_CHECK(hipStreamSynchronize(m->stream));
+    drop_graphs(m);
+    m->norm_mode = mode;
+    return 0;
+}
+
+extern "C" int kcpp_model_set_parallel_block(kcpp_model *m, int on) {
+    if (!m || (on != 0 && on != 1)) { g_err = "parallel_block: 0 or 1"; return -1; }
+    if (on && m->hp.n_expert > 0) { g_err = "parallel_block: a mixture of experts is not supported"; return -1; }
+    RT_CHECK(hipSetDevice(m->device));
+    RT_CHECK(hipStreamSynchronize(m->stream));
+    drop_graphs(m);
+    m->parallel = on != 0;
+    return 0;
+}
+
+extern "C" int kcpp_model_set_logit_scale(kcpp_model *m, float scale) {
+    if (!m || !std::isfinite(scale)) { g_err = "logit_scale: a finite value (0 or 1: none)"; return -1; }
+    RT_CHECK(hipSetDevice(m->device));
+    RT_CHECK(hipStreamSynchronize(m->stream));
+    drop_graphs(m);
+    m->logit_scale = scale;
     return 0;
 }
 
@@ -1136,6 +1169,26 @@ extern "C" int kcpp_model_set_fused_decode(kcpp_model *m, int enable) {
     return 0;
 }
 
+// a norm of the model (attn_norm, ffn_norm, output_norm) by kcpp_model_set_norm_mode: RMS norm or LayerNorm, times w
+static int norm_rows(const kcpp_model *m, const float *x, const float *w, float *y, void *q8k, int64_t T) {
+    const int64_t E = m->hp.n_embd;
+    return m->norm_mode ? kcpp_layer_norm(x, E, w, y, E, q8k, E, T, m->hp.eps, m->stream)
+                        : kcpp_rms_norm(x, E, w, y, E, q8k, E, T, m->hp.eps, m->stream);
+}
+static int norm_rows_q80(const kcpp_model *m, const float *x, const float *w, void *q80, int64_t T, bool tile) {
+    const int64_t E = m->hp.n_embd;
+    if (m->norm_mode) return kcpp_layer_norm_q80(x, E, w, q80, E, T, m->hp.eps, tile, m->stream);
+    return tile ? kcpp_rms_norm_q80t(x, E, w, q80, E, T, m->hp.eps, m->stream) : kcpp_rms_norm_q80(x, E, w, q80, E, T, m->hp.eps, m->stream);
+}
+// the norm and the activation quantization of a fused decode mat-vec that has no instance for it (a LayerNorm prologue
+// outside the row-major K-quant shapes): one launch with the quantizing epilogue, vt = the weight's vec_dot type
+static int norm_act_dec(const kcpp_model *m, const float *x, const float *w, int vt, void *out) {
+    if (vt == KT_Q8_K) return norm_rows(m, x, w, nullptr, out, 1);
+    if (vt == KT_Q8_0) return norm_rows_q80(m, x, w, out, 1, false);
+    g_err = "no norm + quantize launch for this activation type";
+    return -1;
+}
+
 static int mm_launch(int type, const void *W, const void *W2, int64_t K, int64_t N, const void *act, int64_t M, float *Y,
                      int64_t ldy, const float *res, int64_t ldr, int mode, void *ws, hipStream_t s) {
     if (M <= 8 && type != KT_Q8_0_T) return kcpp_gemv(type, W, W2, K, N, act, M, Y, ldy, res, ldr, mode, s);
@@ -1210,7 +1263,7 @@ static int gemm_w_norm(const KTensor &W, const void *act, int64_t M, float *Y, i
 }
 // may the residual GEMM of W at T tokens carry the following rms_norm -> Q8_K (gemm_w_norm)?
 static bool norm_foldable(const kcpp_model *m, const KTensor &W, int T) {
-    return T > 8 && W.rs.empty() && W.type != KT_Q8_0_T && m->lanes.empty() && !m->no_norm_fold;
+    return T > 8 && W.rs.empty() && W.type != KT_Q8_0_T && m->lanes.empty() && !m->no_norm_fold && !m->norm_mode;   // an RMS fold
 }
 
 static int matmul(kcpp_model *m, const KTensor &W, const KTensor *W2, const void *act, int64_t M, float *Y, int64_t ldy,
@@ -1615,10 +1668,10 @@ static int qkv_dec_unfused(kcpp_model *m, KLayer &L, const KTensor *t) {
     for (int j = 1; j <= 3; ++j) {
         const int vt = kcpp_vec_dot_type(t[j].type);
         if (vt != have) {
-            if (vt == KT_Q8_K) {
-                RC(kcpp_rms_norm(m->x, E, (const float *)t[0].d, nullptr, E, m->act, E, 1, hp.eps, s));
+            if (vt == KT_Q8_K || (m->norm_mode && vt == KT_Q8_0)) {
+                RC(norm_act_dec(m, m->x, (const float *)t[0].d, vt, m->act));
             } else {
-                if (!f32_normed) RC(kcpp_rms_norm(m->x, E, (const float *)t[0].d, m->attn, E, nullptr, E, 1, hp.eps, s));
+                if (!f32_normed) RC(norm_rows(m, m->x, (const float *)t[0].d, m->attn, nullptr, 1));
                 f32_normed = true;
                 RC(kcpp_quantize_act(vt, m->attn, E, m->act, E, 1, s));
             }
@@ -1643,6 +1696,7 @@ static int forward_layers_dec(kcpp_model *m) {
     const int64_t E = hp.n_embd, F = hp.n_ff, H = hp.n_head, HKV = hp.n_head_kv, D = E / H, EKV = HKV * D;
     hipStream_t s = m->stream;
     const float kq_scale = 1.0f / sqrtf((float)D);
+    const int npro = m->norm_mode ? 3 : 1;           // the norm prologue of q|k|v, gate|up and the head (gemv_lean.h)
     for (int il = m->il0; il < m->il1; ++il) {
         KLayer &L = m->layers[il - m->il0];
         KTensor tl[10];                              // the layer's tensors; KT_Q8_0_T ones by their KT_Q8_0 decode copies
@@ -1672,9 +1726,10 @@ static int forward_layers_dec(kcpp_model *m) {
             qty[nq++] = ty;
         }
         // q|k|v bias / NeoX pairs (Qwen2): the RS kernels carry them; a launch answering -3 (another weight type, a K
-        // beyond the register-resident shapes) sends the layer's q|k|v through the unfused ops, inside the same graph
-        const bool ex = m->rope_mode != 0 || L.bq;
-        bool unfused = false;
+        // beyond the register-resident shapes) sends the layer's q|k|v through the unfused ops, inside the same graph.
+        // The LayerNorm prologue (Command-R) likewise: instances of the RS kernels only, and none with a bias / NeoX
+        const bool ex = m->rope_mode != 0 || L.bq || m->norm_mode;
+        bool unfused = m->norm_mode && (m->rope_mode != 0 || L.bq);
         if (ex)
             for (int i = 0; i < nq; ++i)
                 unfused |= !(qty[i] == KT_Q4_K_RS || qty[i] == KT_Q5_K_RS || qty[i] == KT_Q6_K_RS);
@@ -1684,17 +1739,17 @@ static int forward_layers_dec(kcpp_model *m) {
             // q|k Q4_K + v Q6_K (Q4_K_M "more bits" layers): one launch (gemv_rs.hip k_gemv_rs_qkv)
             DecArgs c = qa[0];
             c.W[2] = qa[1].W[0]; c.N[2] = qa[1].N[0]; c.role[2] = 2; c.bias[2] = qa[1].bias[0]; c.nseg = 3;
-            mixed_rc = kcpp_gemv_rs_qkv_mixed(&c, s);
+            mixed_rc = kcpp_gemv_rs_qkv_mixed_pro(&c, npro, s);
             if (mixed_rc != -3 && mixed_rc != -5) RC(mixed_rc);
         }
-        if (mixed_rc != 0 && nq == 2 && qty[1] == KT_Q8_0 && !m->no_dual_qkv) {
+        if (mixed_rc != 0 && nq == 2 && qty[1] == KT_Q8_0 && !m->no_dual_qkv && !m->norm_mode) {
             // q in an RS layout + k|v in Q8_0 (Mixtral's Q5_K_M policy): both launches' workgroups in one grid
             mixed_rc = kcpp_gemv_qkv_dual(&qa[0], qty[0], &qa[1], s);
             if (mixed_rc != -3 && mixed_rc != -5) RC(mixed_rc);
         }
         if (mixed_rc != 0)
             for (int i = 0; i < nq && !unfused; ++i) {
-                const int rc = kcpp_gemv_dec(qty[i], &qa[i], 2, 1, 2, s);
+                const int rc = kcpp_gemv_dec(qty[i], &qa[i], 2, npro, 2, s);
                 if (rc == -3 && ex) unfused = true;       // (a launch before it wrote what the unfused ops write again)
                 else RC(rc);
             }
@@ -1707,7 +1762,7 @@ static int forward_layers_dec(kcpp_model *m) {
         else
             RC(kcpp_flash_attn(m->q16, L.kc, L.vc, m->attn, nullptr, m->fa_ws, 1, (int)H, (int)HKV, (int)D, 0, m->pos_dev,
                                hp.n_ctx, kq_scale, m->dec_short && D == 128 ? 7 : 1, s));
-        {   // x += wo . attn
+        auto wo_step = [&]() -> int {   // x += wo . attn
             DecArgs a;
             memset(&a, 0, sizeof a);
             a.K = E; a.nseg = 1;
@@ -1720,22 +1775,56 @@ static int forward_layers_dec(kcpp_model *m) {
                 rc = kcpp_gemv_dec(t[4].type, &a, 0, 0, gemv_rows_per_wave(t[4].N, 0), s);
             }
             RC(rc);
-        }
+            return 0;
+        };
+        // Command-R's parallel block: the FFN reads attn_norm(x) like q|k|v, so gate|up runs before anything has
+        // modified x, then down and wo each add onto x: wo . a + (ffn + x), the reference's (ffn + x) + attn_out
+        if (!m->parallel) RC(wo_step());
         if (hp.n_expert > 0) { RC(moe_dec(m, L)); continue; }
-        // --- ffn_norm + gate|up + silu*mul
+        // --- ffn_norm (parallel block: attn_norm) + gate|up + silu*mul
+        const float *fnw = (const float *)t[m->parallel ? 0 : 5].d;
+        // gate / up of a LayerNorm model where the prologue has no instance (-3): the norm's quantizing launch, then the
+        // mat-vecs on that activation (PRO 0); j = 6 / 7 into y, or both with the GLU epilogue (mode 1)
+        auto glu_unfused = [&](int j, int mode, float *y) -> int {
+            DecArgs a;
+            memset(&a, 0, sizeof a);
+            a.K = E; a.nseg = 1; a.W[0] = (const uint8_t *)t[j].d; a.N[0] = F; a.Y[0] = y;
+            if (mode == 1) a.W2 = (const uint8_t *)t[7].d;
+            a.act = (const uint8_t *)m->act;
+            return kcpp_gemv_dec(t[j].type, &a, mode, 0, gemv_rows_per_wave(F, mode), s);
+        };
+        bool glu_done = false;
         if (t[6].type == t[7].type) {
             DecArgs a;
             memset(&a, 0, sizeof a);
-            a.K = E; a.x = m->x; a.nw = (const float *)t[5].d; a.eps = hp.eps; a.nseg = 1;
+            a.K = E; a.x = m->x; a.nw = fnw; a.eps = hp.eps; a.nseg = 1;
             a.W[0] = (const uint8_t *)t[6].d; a.W2 = (const uint8_t *)t[7].d; a.N[0] = F; a.Y[0] = m->h;
-            RC(kcpp_gemv_dec(t[6].type, &a, 1, 1, gemv_rows_per_wave(F, 1), s));
-        } else {
+            int rc = kcpp_gemv_dec(t[6].type, &a, 1, npro, gemv_rows_per_wave(F, 1), s);
+            if (rc == -3 && m->norm_mode) {
+                RC(norm_act_dec(m, m->x, fnw, kcpp_vec_dot_type(t[6].type), m->act));
+                rc = glu_unfused(6, 1, m->h);
+                if (rc == -3 || rc == -7) rc = 1;     // no PRO 0 GLU kernel for the type: gate and up on their own
+            }
+            if (rc != 1) { RC(rc); glu_done = true; }
+        }
+        if (!glu_done) {
+            int have = -1;
             for (int j = 6; j <= 7; ++j) {
-                DecArgs a;
-                memset(&a, 0, sizeof a);
-                a.K = E; a.x = m->x; a.nw = (const float *)t[5].d; a.eps = hp.eps; a.nseg = 1;
-                a.W[0] = (const uint8_t *)t[j].d; a.N[0] = F; a.Y[0] = j == 6 ? m->h : m->qkv;
-                RC(kcpp_gemv_dec(t[j].type, &a, 0, 1, gemv_rows_per_wave(F, 0), s));
+                float *y = j == 6 ? m->h : m->qkv;
+                if (!m->norm_mode) {
+                    DecArgs a;
+                    memset(&a, 0, sizeof a);
+                    a.K = E; a.x = m->x; a.nw = fnw; a.eps = hp.eps; a.nseg = 1;
+                    a.W[0] = (const uint8_t *)t[j].d; a.N[0] = F; a.Y[0] = y;
+                    RC(kcpp_gemv_dec(t[j].type, &a, 0, 1, gemv_rows_per_wave(F, 0), s));
+                    continue;
+                }
+                const int vt = kcpp_vec_dot_type(t[j].type);
+                if (vt != have) RC(norm_act_dec(m, m->x, fnw, vt, m->act));
+                have = vt;
+                int rc = glu_unfused(j, 0, y);
+                if (rc == -3 || rc == -8) rc = kcpp_gemv(t[j].type, t[j].d, nullptr, E, F, m->act, 1, y, F, nullptr, 0, 0, s);
+                RC(rc);
             }
             RC(kcpp_silu_mul(m->h, m->h, m->qkv, F, s));
         }
@@ -1752,8 +1841,16 @@ static int forward_layers_dec(kcpp_model *m) {
                 RC(rc);
             }
         }
+        if (m->parallel) RC(wo_step());
     }
     return 0;
+}
+
+// the logit scale of kcpp_model_set_logit_scale, directly behind the head's mat-vec (inside the captured graph): every
+// reader of m->logits -- the device argmax, the candidate front end, the masked argmax, the host copy -- sees scaled values
+static int scale_logits(kcpp_model *m) {
+    if (m->logit_scale == 0.0f || m->logit_scale == 1.0f) return 0;
+    return kcpp_scale(m->logits, m->logit_scale, m->hp.n_vocab, m->stream);
 }
 
 static int head_dec(kcpp_model *m) {
@@ -1761,7 +1858,18 @@ static int head_dec(kcpp_model *m) {
     memset(&a, 0, sizeof a);
     a.K = m->hp.n_embd; a.x = m->x; a.nw = (const float *)m->output_norm.d; a.eps = m->hp.eps; a.nseg = 1;
     a.W[0] = (const uint8_t *)(m->output.dec ? m->output.dec : m->output.d); a.N[0] = m->hp.n_vocab; a.Y[0] = m->logits;
-    return kcpp_gemv_dec(m->output.dec ? KT_Q8_0 : m->output.type, &a, 0, 1, gemv_rows_per_wave(m->hp.n_vocab, 0), m->stream);
+    const int type = m->output.dec ? KT_Q8_0 : m->output.type;
+    const int rpw = gemv_rows_per_wave(m->hp.n_vocab, 0);
+    int rc = kcpp_gemv_dec(type, &a, 0, m->norm_mode ? 3 : 1, rpw, m->stream);
+    if (rc == -3 && m->norm_mode) {      // no LayerNorm prologue for this head: the norm's quantizing launch, then PRO 0
+        RC(norm_act_dec(m, m->x, a.nw, kcpp_vec_dot_type(type), m->act));
+        a.x = nullptr; a.nw = nullptr; a.act = (const uint8_t *)m->act;
+        rc = kcpp_gemv_dec(type, &a, 0, 0, rpw, m->stream);
+        if (rc == -3 || rc == -8)
+            rc = kcpp_gemv(type, a.W[0], nullptr, a.K, a.N[0], m->act, 1, m->logits, a.N[0], nullptr, 0, 0, m->stream);
+    }
+    RC(rc);
+    return scale_logits(m);
 }
 
 // run layers [il0, il1) on m->x for T tokens (T <= ub).  n_past via pos_dev when graph-replayed.
@@ -1785,9 +1893,14 @@ static int forward_layers(kcpp_model *m, int T, int n_past, bool dev_pos) {
         bool roped = false;                          // q16 and this step's K/V rows already written
         const bool normed = pre_normed;
         pre_normed = false;
+        // what m->act holds once q|k|v has run (a vec_dot type), and whether m->attn holds the f32 normalised rows: the
+        // parallel block's FFN reads the same attn_norm(x)
+        int act_vt = -1;
+        bool f32_normed = false;
         // attn_norm -> act (Q8_K fused, or f32 then Q8_0)
         if (qkv_q8k(t)) {
-            if (!normed) RC(kcpp_rms_norm(m->x, E, (const float *)t[0].d, nullptr, E, m->act, E, T, hp.eps, s));
+            if (!normed) RC(norm_rows(m, m->x, (const float *)t[0].d, nullptr, m->act, T));
+            act_vt = KT_Q8_K;
             if (L.nqkv >= 2) {                       // q|k(|v) rows back to back: one GEMM
                 KTensor f = t[1];
                 f.N = E + (L.nqkv - 1) * EKV;
@@ -1814,7 +1927,8 @@ static int forward_layers(kcpp_model *m, int T, int n_past, bool dev_pos) {
                 RC(matmul(m, t[3], nullptr, m->act, T, m->qkv + E + EKV, LQ, nullptr, 0, 0));
             }
         } else if (m->q80t) {                        // Q8_0 tile layout: norm + TA quantization, one q|k|v launch
-            RC(kcpp_rms_norm_q80t(m->x, E, (const float *)t[0].d, m->act, E, T, hp.eps, s));
+            RC(norm_rows_q80(m, m->x, (const float *)t[0].d, m->act, T, true));
+            act_vt = KT_Q8_0_TA;
             if (m->lanes.empty()) {
                 const void *Wq[3] = {t[1].d, t[2].d, t[3].d};
                 const int64_t Nq[3] = {E, EKV, EKV};
@@ -1831,16 +1945,53 @@ static int forward_layers(kcpp_model *m, int T, int n_past, bool dev_pos) {
             }
         } else if (T > 8 && T <= 32 && m->lanes.empty() && t[1].type == KT_Q8_0 && t[2].type == KT_Q8_0 && t[3].type == KT_Q8_0 && E % 128 == 0 &&
                    EKV % 128 == 0) {                 // small-batch Q8_0: one quantization, one q|k|v launch
-            RC(kcpp_rms_norm_q80(m->x, E, (const float *)t[0].d, m->act, E, T, hp.eps, s));
+            RC(norm_rows_q80(m, m->x, (const float *)t[0].d, m->act, T, false));
+            act_vt = KT_Q8_0;
             const void *Wq[3] = {t[1].d, t[2].d, t[3].d};
             const int64_t Nq[3] = {E, EKV, EKV};
             RC(kcpp_gemm_q80_segs(Wq, Nq, 3, E, m->act, T, m->qkv, LQ, m->gemm_ws, s));
         } else {
-            RC(kcpp_rms_norm(m->x, E, (const float *)t[0].d, m->attn, E, nullptr, E, T, hp.eps, s));
+            RC(norm_rows(m, m->x, (const float *)t[0].d, m->attn, nullptr, T));
+            f32_normed = true;
             for (int j = 1; j <= 3; ++j) {
-                RC(kcpp_quantize_act(kcpp_vec_dot_type(t[j].type), m->attn, E, m->act, E, T, s));
+                act_vt = kcpp_vec_dot_type(t[j].type);
+                RC(kcpp_quantize_act(act_vt, m->attn, E, m->act, E, T, s));
                 const int64_t off = j == 1 ? 0 : (j == 2 ? E : E + EKV);
                 RC(matmul(m, t[j], nullptr, m->act, T, m->qkv + off, LQ, nullptr, 0, 0));
+            }
+        }
+        if (m->parallel) {
+            // Command-R's parallel block: gate|up on attn_norm(x) here, while m->act (and m->attn) still hold it -- the
+            // activation q|k|v used where the vec_dot types agree, else a second quantization of the same normalised rows
+            // -- leaving down's activation in m->act2; down and wo add onto x after the attention
+            auto act_for = [&](int vt) -> int {
+                if (act_vt == vt) return 0;
+                if (!f32_normed) RC(norm_rows(m, m->x, (const float *)t[0].d, m->attn, nullptr, T));
+                f32_normed = true;
+                act_vt = vt;
+                return kcpp_quantize_act(vt, m->attn, E, m->act, E, T, s);
+            };
+            const int vd = kcpp_vec_dot_type(t[8].type);
+            if (m->q80t && m->lanes.empty()) {
+                RC(act_for(KT_Q8_0_TA));
+                RC(kcpp_gemm_q80t(&t[6].d, &F, 1, t[7].d, E, m->act, T, nullptr, 0, nullptr, 0, 1, m->act2, m->gemm_ws, s));
+            } else if (L.glu_fused && vd == KT_Q8_K) {
+                RC(act_for(kcpp_vec_dot_type(t[6].type)));
+                KTensor f = t[6];
+                f.N = 2 * F;
+                RC(matmul(m, f, nullptr, m->act, T, m->hglu, 2 * F, nullptr, 0, 0));
+                RC(kcpp_quantize_act_glu(m->hglu, 2 * F, F, m->act2, F, T, s));
+            } else {
+                RC(act_for(kcpp_vec_dot_type(t[6].type)));
+                if (t[6].type == t[7].type) {
+                    RC(matmul(m, t[6], &t[7], m->act, T, m->h, F, nullptr, 0, 1));          // h = silu(g) * u
+                } else {
+                    RC(matmul(m, t[6], nullptr, m->act, T, m->h, F, nullptr, 0, 0));
+                    RC(act_for(kcpp_vec_dot_type(t[7].type)));
+                    RC(matmul(m, t[7], nullptr, m->act, T, m->hglu, F, nullptr, 0, 0));
+                    RC(kcpp_silu_mul(m->h, m->h, m->hglu, (int64_t)T * F, s));
+                }
+                RC(kcpp_quantize_act(vd, m->h, F, m->act2, F, T, s));
             }
         }
         const bool kvq = m->kv_tk != KT_F16;
@@ -1879,6 +2030,11 @@ static int forward_layers(kcpp_model *m, int T, int n_past, bool dev_pos) {
         if (!(woq && T <= 16) && !attn_q) RC(kcpp_quantize_act(kcpp_vec_dot_type(t[4].type), m->attn, E, m->act, E, T, s));
         const bool gq = kcpp_vec_dot_type(t[6].type) == KT_Q8_K && kcpp_vec_dot_type(t[7].type) == KT_Q8_K;
         // x += wo . attn; dense Q8_K FFNs: ffn_norm's activation formed with it (in wo's split-K reduce)
+        if (m->parallel) {                           // (ffn + x) + attn_out: down, then wo, each with res = x
+            RC(matmul(m, t[8], nullptr, m->act2, T, m->x, E, m->x, E, 0));
+            RC(matmul(m, t[4], nullptr, m->act, T, m->x, E, m->x, E, 0));
+            continue;
+        }
         const bool wo_norm = hp.n_expert <= 0 && !m->q80t && gq && norm_foldable(m, t[4], T);
         if (wo_norm)
             RC(gemm_w_norm(t[4], m->act, T, m->x, E, m->x, E, m->gemm_ws, s, (const float *)t[5].d, hp.eps, m->act));
@@ -1888,7 +2044,7 @@ static int forward_layers(kcpp_model *m, int T, int n_past, bool dev_pos) {
         if (m->q80t) {
             // ffn_norm -> TA quantization; gate|up with silu(g) u quantized to the TA activation of down in the GEMM's
             // epilogue (one launch); down with the residual
-            RC(kcpp_rms_norm_q80t(m->x, E, (const float *)t[5].d, m->act, E, T, hp.eps, s));
+            RC(norm_rows_q80(m, m->x, (const float *)t[5].d, m->act, T, true));
             if (m->lanes.empty()) {
                 RC(kcpp_gemm_q80t(&t[6].d, &F, 1, t[7].d, E, m->act, T, nullptr, 0, nullptr, 0, 1, m->act2, m->gemm_ws, s));
             } else {
@@ -1899,11 +2055,11 @@ static int forward_layers(kcpp_model *m, int T, int n_past, bool dev_pos) {
             continue;
         }
         if (gq) {
-            if (!wo_norm) RC(kcpp_rms_norm(m->x, E, (const float *)t[5].d, nullptr, E, m->act, E, T, hp.eps, s));
+            if (!wo_norm) RC(norm_rows(m, m->x, (const float *)t[5].d, nullptr, m->act, T));
         } else if (kcpp_vec_dot_type(t[6].type) == KT_Q8_0 && kcpp_vec_dot_type(t[7].type) == KT_Q8_0) {
-            RC(kcpp_rms_norm_q80(m->x, E, (const float *)t[5].d, m->act, E, T, hp.eps, s));
+            RC(norm_rows_q80(m, m->x, (const float *)t[5].d, m->act, T, false));
         } else {
-            RC(kcpp_rms_norm(m->x, E, (const float *)t[5].d, m->attn, E, nullptr, E, T, hp.eps, s));
+            RC(norm_rows(m, m->x, (const float *)t[5].d, m->attn, nullptr, T));
             RC(kcpp_quantize_act(kcpp_vec_dot_type(t[6].type), m->attn, E, m->act, E, T, s));
         }
         if (L.glu_fused && kcpp_vec_dot_type(t[8].type) == KT_Q8_K) {
@@ -1941,13 +2097,13 @@ static int head(kcpp_model *m, int T) {
     const int64_t E = hp.n_embd;
     const float *last = m->x + (int64_t)(T - 1) * E;
     if (kcpp_vec_dot_type(m->output.type) == KT_Q8_K) {
-        RC(kcpp_rms_norm(last, E, (const float *)m->output_norm.d, nullptr, E, m->act, E, 1, hp.eps, m->stream));
+        RC(norm_rows(m, last, (const float *)m->output_norm.d, nullptr, m->act, 1));
     } else {
-        RC(kcpp_rms_norm(last, E, (const float *)m->output_norm.d, m->attn, E, nullptr, E, 1, hp.eps, m->stream));
+        RC(norm_rows(m, last, (const float *)m->output_norm.d, m->attn, nullptr, 1));
         RC(kcpp_quantize_act(kcpp_vec_dot_type(m->output.type), m->attn, E, m->act, E, 1, m->stream));
     }
     RC(matmul(m, m->output, nullptr, m->act, 1, m->logits, hp.n_vocab, nullptr, 0, 0));
-    return 0;
+    return scale_logits(m);
 }
 
 // full single-token step with the inputs read from device memory (graph-capturable)

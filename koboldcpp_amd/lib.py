@@ -63,6 +63,13 @@ _SIGS = {
     "kcpp_kv_shift_rows_ex": [P, P, P, P, I64, I, P, I, P],
     "kcpp_rope_qk_inplace_ex": [P, I64, I, I, I, I, I, P, P, I, P, P, P, P],
     "kcpp_model_set_rope_mode": [P, I],
+    "kcpp_model_set_norm_mode": [P, I],
+    "kcpp_model_set_parallel_block": [P, I],
+    "kcpp_model_set_logit_scale": [P, Fl],
+    "kcpp_layer_norm": [P, I64, P, P, I64, P, I64, I64, Fl, P],
+    "kcpp_layer_norm_q80": [P, I64, P, P, I64, I64, Fl, I, P],
+    "kcpp_scale": [P, Fl, I64, P],
+    "kcpp_gemv_rs_qkv_mixed_pro": [P, I, P],
     "kcpp_model_set_qkv_bias": [P, I, P, P, P],
     "kcpp_flash_attn": [P, P, P, P, P, P, I, I, I, I, I, P, I, Fl, I, P],
     "kcpp_flash_attn_prefill_mfma": [P, P, P, P, I, I, I, I, I, Fl, P],
@@ -72,6 +79,7 @@ _SIGS = {
     "kcpp_fa_decode_plan": [I, I, I, I, I, I, I, I, I, I, P],
     "kcpp_gemv_dec_plan": [I, I, I64, I, I64, I64, I64, I, I, I, I, I, I, I, I, I, I, P],
     "kcpp_gemv_qkv_mixed_plan": [I64, I64, I64, I64, I, I, I, I, I, P],
+    "kcpp_gemv_qkv_mixed_plan_pro": [I64, I64, I64, I64, I, I, I, I, I, I, P],
     "kcpp_gemv_qkv_dual_plan": [I, I64, I, P, I, I64, I, P, I, P],
     "kcpp_flash_attn_dec_ta": [P, P, P, P, P, P, I, I, I, I, P, I, Fl, P],
     "kcpp_fa_decode_ex": [P, P, P, I64, I64, P, P, P, I, I, I, P, I, Fl, I, P],
@@ -433,6 +441,18 @@ class Model:
         """0 = NORM pairs (Llama, the default), 2 = NeoX pairs (Qwen2)"""
         _chk(_L.kcpp_model_set_rope_mode(self.m, int(mode)), "set_rope_mode")
 
+    def set_norm_mode(self, mode):
+        """0 = RMS norm (the default), 1 = LayerNorm for attn_norm and output_norm (Command-R; eps = layer_norm_epsilon)"""
+        _chk(_L.kcpp_model_set_norm_mode(self.m, int(mode)), "set_norm_mode")
+
+    def set_parallel_block(self, on):
+        """attention and the FFN both read attn_norm(x); layer output (ffn_out + x) + attn_out (Command-R)"""
+        _chk(_L.kcpp_model_set_parallel_block(self.m, int(bool(on))), "set_parallel_block")
+
+    def set_logit_scale(self, scale):
+        """every logit times scale where the head writes them (Command-R logit_scale); 0 or 1 = none"""
+        _chk(_L.kcpp_model_set_logit_scale(self.m, float(scale)), "set_logit_scale")
+
     def set_qkv_bias(self, il, bq, bk, bv):
         """q / k / v projection biases of layer il (float32 n_embd, n_embd_gqa, n_embd_gqa); all None clears them"""
         import numpy as np
@@ -601,9 +621,14 @@ def gemv_dec_plan(entry, wtype, K, N, mode, pro, rows_per_wave=1, flags=(), role
     return d
 
 
-def gemv_qkv_mixed_plan(K, N, flags=(), role=(0, 1, 2), D=0):
+def gemv_qkv_mixed_plan(K, N, flags=(), role=(0, 1, 2), D=0, pro=None):
     """what kcpp_gemv_rs_qkv_mixed launches (host only): its error code, or a dict of NIA, NIB, MC, EX, block, nblk,
-    lds_bytes"""
+    lds_bytes; with pro (1 = rms_norm, 3 = LayerNorm) kcpp_gemv_rs_qkv_mixed_pro's, the dict then holds PRO too"""
+    if pro is not None:
+        out = (ctypes.c_int32 * 9)()
+        rc = _L.kcpp_gemv_qkv_mixed_plan_pro(int(K), N[0], N[1], N[2], role[0], role[1], role[2], int(D), _gemv_flags(flags),
+                                             int(pro), out)
+        return rc if rc else dict(zip(("rc", "NIA", "NIB", "MC", "EX", "block", "nblk", "lds_bytes", "PRO"), out))
     out = (ctypes.c_int32 * 8)()
     rc = _L.kcpp_gemv_qkv_mixed_plan(int(K), N[0], N[1], N[2], role[0], role[1], role[2], int(D), _gemv_flags(flags), out)
     return rc if rc else dict(zip(("rc", "NIA", "NIB", "MC", "EX", "block", "nblk", "lds_bytes"), out))
